@@ -17,18 +17,28 @@ ranks itself -- fresh child processes through ``torch.distributed.run``, before 
 process has touched a GPU -- and relays rank 0's line; it never reports a 1-GPU run for an
 N-GPU request.
 
-Timing: blocks of EXACTLY ``--steps`` (K) steps are run back to back -- ``reps`` of them,
-enough for >= 50 ms of GPU time (``--reps`` overrides) -- inside ONE region bracketed by
-barrier + synchronize on both sides.  Blocks are hipGraph replays; a K shorter than the
-256-step graph window shares one replay with the next blocks (``blocks_per_replay``), so the
-~10 us between two graph launches is not charged to 20 steps.  A HIP event on the launch
-stream separates the replays; ``ms_per_step`` is the MEDIAN block time / K (MAX over ranks):
-a short ``--steps`` gives the steady-state number, not one launch + sync latency.  The wall
+Timing: the timed region runs EXACTLY ``--steps`` (K) steps, bracketed by barrier +
+synchronize on both sides (``--reps R``: R blocks of K steps back to back, R x K steps;
+``--reps 0``: enough blocks for >= 50 ms of GPU time).  Blocks are hipGraph replays; with R > 1 a K shorter
+than the 256-step graph window shares one replay with the next blocks (``blocks_per_replay``), so
+the ~10 us between two graph launches is not charged to 20 steps.  A HIP event on the launch
+stream separates the replays; ``ms_per_step`` is the MEDIAN block time / K (MAX over ranks; with
+one block, the region's GPU time / K).  The wall
 clock over the whole region is reported beside it (``ms_per_step_wall``; for N > 1 it is the
 value).  The host POLLS the last event instead of blocking on it: a blocked wait on this box
 sometimes returns 50-80 ms after the device has finished (tools/slow_stretch_probe4.py) -- what
 round 2 took for a "slow stretch" of the GPU and hid behind 150 ms of untimed replays.  A short
-untimed settle (``--settle-ms``, 30 ms: the first replays of a freshly instantiated graph) remains.
+untimed settle (``--settle-ms``, 30 ms: the first replays of a freshly instantiated graph) remains;
+after it the device state is put back to what it was before the warm-up, so the timed region starts
+from the same state in every run with the same arguments.
+
+A plain run sets up, warms up, times and prints.  ``--full`` adds what the headline does not need:
+the CPU baseline (``cpu_baseline``: the C oracle on the host cores, ~15 s, and the reference's
+recorded Python rate), the stored PMC traffic of ``profiles/traffic.json`` and an event-bracketed
+probe of 200 eager launches (``roofline.traffic`` / ``avg_launch_us_event_bracketed``).
+
+``--dump-outputs DIR`` writes what the last timed step returned (``step_outputs``) as
+``DIR/<name>.npy`` (rank 0's shard), so two builds can be compared output for output.
 
 ``--decompose`` replays the same graph on the TIMELINE build of the level's library (every wave
 stamps the chip-wide 100 MHz clock; include/oc_hip.h: oc_timeline_begin) and adds
@@ -64,6 +74,7 @@ WINDOW = 256                # pre-generated action steps, cycled
 MIN_TIMED_MS = 50.0         # GPU time the timed region must cover (reps is derived from it)
 SETTLE_MS = 30.0         # untimed replays before calibration and timing (--settle-ms; see main)
 ELEM = {"int32": 4, "int8": 1, "float32": 4}
+DUMP_BYTES = 60 << 20       # --dump-outputs: at most this many bytes of arrays (+ .npy headers) in all
 
 
 def survey_bytes_per_env_step(A, M, S, C, with_obs, obs_elem=4):
@@ -101,8 +112,16 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=2048)
     p.add_argument("--warmup", type=int, default=256)
-    p.add_argument("--reps", type=int, default=0,
-                   help="timed repetitions of the --steps block (0 = enough for %.0f ms of GPU time)" % MIN_TIMED_MS)
+    p.add_argument("--reps", type=int, default=1,
+                   help="timed repetitions of the --steps block: the timed region is reps x steps steps "
+                        "(0 = enough blocks for %.0f ms of GPU time)" % MIN_TIMED_MS)
+    p.add_argument("--full", action="store_true",
+                   help="also what the headline does not need: the CPU baseline (C oracle on the host cores + "
+                        "the recorded reference rate), stored PMC traffic, an event-bracketed eager-launch probe")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed region, write what its last step returned as DIR/<name>.npy (float32, "
+                        "float64 where the step computes float64; a fixed sample of envs beyond %d MB)"
+                        % (DUMP_BYTES >> 20))
     p.add_argument("--mode", default="open-loop", choices=["open-loop", "closed-loop"])
     p.add_argument("--level", default="open-divider_tomato")
     p.add_argument("--agents", type=int, default=2)
@@ -439,6 +458,55 @@ class StepBlocks:
             self.step_fn(k)
 
 
+def save_state(env, tensors=(), players=()):
+    """Copies of the mutable device state of the timed path -- the env's arena (state, comm, outputs),
+    its placement stream, further `tensors` (the closed loop's action rows), the players' streams and
+    pending pairs, torch's CUDA generator -- and a function that puts them back.  The settle replays run
+    for a time, not a count of steps; rewinding after them makes the timed region start from the same
+    state in every run with the same arguments, so its outputs can be compared run for run."""
+    keep = [(t, t.clone()) for t in (env._arena, env.rng) + tuple(tensors) if t is not None]
+    held = [(pl, pl.get_state(env.n)) for pl in players if hasattr(pl, "get_state")]
+    torch_rng = torch.cuda.get_rng_state(env.device)
+
+    def restore():
+        for t, v in keep:
+            t.copy_(v)
+        for pl, st in held:
+            pl.set_state(st)
+        torch.cuda.set_rng_state(torch_rng, env.device)
+    return restore
+
+
+def step_outputs(env, wrapper, closed):
+    """What one step of the timed path hands its caller (device views the next step overwrites),
+    each with the env axis last: ``ClosedLoop.step`` -> the ego's observation rows, shaped reward,
+    done; ``multi_step`` -> both viewers' observation rows, timestep, shaped reward, done; ``step``
+    (3+ agents) -> reward, done, the two shaping terms."""
+    if closed:
+        return {"obs": env.obs[0], "shaped_reward": env.shaped_reward, "done": env.done}
+    if wrapper:
+        return {"obs": env.obs, "timestep": env.timestep, "shaped_reward": env.shaped_reward, "done": env.done}
+    return {"reward": env.reward, "done": env.done, "shaping": env.shaping}
+
+
+def dump_outputs(outputs, path, limit=DUMP_BYTES, seed=0):
+    """Write every array of `outputs` (name -> tensor, env axis last) as path/<name>.npy: float64
+    arrays as float64, all others (int32 / int8 / float32; integers below 2^24, so exactly) as float32.
+    Beyond `limit` bytes in all, every array keeps the same fixed, seeded, sorted sample of envs.
+    Returns {name: shape written}."""
+    arrs = {k: v.cpu().numpy() for k, v in outputs.items()}
+    arrs = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrs.items()}
+    n = next(iter(arrs.values())).shape[-1]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > limit:
+        idx = np.sort(np.random.default_rng(seed).choice(n, max(1, n * limit // total), replace=False))
+        arrs = {k: a[..., idx] for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrs.items()}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -514,11 +582,17 @@ def main():
     # one graph replay (bpr * K <= G steps) and the replay time is divided by bpr.
     bpr = max(1, G // K) if use_graph else 1
     SB = bpr * K
+    # the timed region: `reps` blocks of EXACTLY K steps, bpr of them per replay (the last replay may carry
+    # fewer); --reps 0: whole replays, as many as the calibration below asks for
+    units = [min(bpr, args.reps - i) for i in range(0, args.reps, bpr)] if args.reps > 0 else None
+    lengths = sorted({u * K for u in units}) if units else [SB]
     with torch.cuda.stream(stream):
+        restore = save_state(env, tensors=(venv._act,) if closed else (),
+                             players=(ego, venv.partner) if closed else ())
         for k in range(max(1, min(args.warmup, 64))):    # touch everything before capture (module load,
             step_fn(k)                                   # first-launch work): at least once, also for --warmup 0
         stream.synchronize()
-        blocks.prepare((args.warmup, SB))
+        blocks.prepare((args.warmup,) + tuple(lengths))
         blocks.run(args.warmup)
         stream.synchronize()
         # settle: a few untimed replays of the freshly instantiated graphs on top of the `--warmup`
@@ -530,13 +604,12 @@ def main():
         # wall-clock loops did.  DESIGN.md section 7.)
         t_settle = time.perf_counter()
         while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
-            blocks.run(SB)
+            for length in lengths:
+                blocks.run(length)
             stream.synchronize()
 
-        # reps: enough blocks for MIN_TIMED_MS of GPU time, from a short calibration
-        if args.reps > 0:
-            replays = max(1, -(-args.reps // bpr))
-        else:
+        # --reps 0: enough blocks for MIN_TIMED_MS of GPU time, from a short calibration
+        if units is None:
             c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ncal = max(1, min(8, 4096 // SB))
             c0.record(stream)
@@ -546,9 +619,12 @@ def main():
             stream.synchronize()
             replay_ms = max(c0.elapsed_time(c1) / ncal, 1e-3)
             replays = int(min(4096, max(5, math.ceil(MIN_TIMED_MS / replay_ms))))
-        replays = int(ocdist.reduce_max([float(replays)], dev if args.backend == "nccl" else None)[0])
-        reps = replays * bpr                             # K-step blocks in the timed region
+            replays = int(ocdist.reduce_max([float(replays)], dev if args.backend == "nccl" else None)[0])
+            units = [bpr] * replays
+        replays = len(units)
+        reps = sum(units)                                # K-step blocks in the timed region
 
+        restore()                                        # the timed region starts from the state set up above
         if env.metrics is not None:
             env.metrics.zero_()
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(replays + 1)]
@@ -558,8 +634,8 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         evs[0].record(stream)
-        for r in range(replays):
-            blocks.run(SB)                               # bpr blocks of EXACTLY K steps each
+        for r, u in enumerate(units):
+            blocks.run(u * K)                            # u blocks of EXACTLY K steps each
             evs[r + 1].record(stream)
         # The host learns of the end of the region by POLLING the last event, not by a blocking wait:
         # on this box a blocked hipEventSynchronize / hipDeviceSynchronize sometimes returns 50-80 ms
@@ -574,15 +650,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
-        block_s = sorted(evs[r].elapsed_time(evs[r + 1]) / 1e3 / bpr for r in range(replays))
+        block_s = sorted(evs[r].elapsed_time(evs[r + 1]) / 1e3 / u for r, u in enumerate(units))
         med_block_s = (block_s[replays // 2] if replays % 2
                        else 0.5 * (block_s[replays // 2 - 1] + block_s[replays // 2]))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(step_outputs(env, wrapper, closed), args.dump_outputs)
         rollout_metrics = env.metrics_vector()          # before the probe launches below
 
-        # kernel duration cross-check: HIP events on the launch stream around individual
+        # kernel duration cross-check (--full): HIP events on the launch stream around individual
         # eager launches, trimmed mean (open-loop only: a closed-loop step is several kernels)
         launch_ms_bracketed = None
-        if not closed:
+        if args.full and not closed:
             probe = 200
             e0 = [torch.cuda.Event(enable_timing=True) for _ in range(probe)]
             e1 = [torch.cuda.Event(enable_timing=True) for _ in range(probe)]
@@ -621,7 +699,7 @@ def main():
         survey_gbps = survey * n / med_step_s / 1e9
         traffic = traffic_src = None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath) and not closed:
+        if args.full and os.path.exists(tpath) and not closed:
             try:
                 with open(tpath) as f:
                     tj = json.load(f)
@@ -677,7 +755,7 @@ def main():
                                "between replays, MAX over ranks",
                        "value_from": ("median block time (N = 1)" if world == 1 else
                                       "barrier-bracketed wall clock over the region, MAX over ranks (N > 1)"),
-                       "blocks_per_replay": bpr, "replays": replays, "settle_ms_untimed": args.settle_ms,
+                       "blocks_per_replay": units[0], "replays": replays, "settle_ms_untimed": args.settle_ms,
                        "block_ms_min": block_s[0] * 1e3, "block_ms_median": med_block_s * 1e3,
                        "block_ms_max": block_s[-1] * 1e3, "region_wall_s": wall,
                        "region_gpu_span_s": evs[0].elapsed_time(evs[-1]) / 1e3},
@@ -701,7 +779,7 @@ def main():
                 "frac_survey_bytes": (survey_gbps / HBM_PEAK_GBPS) if survey_gbps <= HBM_PEAK_GBPS else None,
                 "kernel": kernel,
                 "avg_launch_us_timed_region": med_step_s * 1e6,
-                "avg_launch_us_event_bracketed": launch_ms_bracketed * 1e3}
+                "avg_launch_us_event_bracketed": None if launch_ms_bracketed is None else launch_ms_bracketed * 1e3}
             if decomp is not None:
                 # the step as the chip saw it (timeline build): kernel-active + boundary = period, to be
                 # read against ms_per_step of the product build above
@@ -717,13 +795,14 @@ def main():
                     "frac_kernel_active": (rd + wr) * n / (act_prod * 1e-6) / 1e9 / HBM_PEAK_GBPS,
                     "decompose": decomp,
                     "decompose_closure": (decomp["kernel_active_us"] + decomp["boundary_us"]) / (med_step_s * 1e6)})
-        if not args.no_cpu_baseline and world == 1 and not closed:
+        if args.full and not args.no_cpu_baseline and world == 1 and not closed:
             out["cpu_baseline"] = cpu_baseline(lv.blob, lv.num_agents, args.comm, wrapper,
                                                args.cpu_seconds)
             out["cpu_baseline"]["reference_python"] = reference_python_rate(args.level, args.agents, wrapper)
         else:
             out["cpu_baseline"] = {"skipped": "N>1" if world > 1 else
-                                   "closed-loop mode" if closed else "--no-cpu-baseline"}
+                                   "closed-loop mode" if closed else
+                                   "--no-cpu-baseline" if args.no_cpu_baseline else "measured with --full"}
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -537,6 +537,40 @@ def test_bench_byte_accounting():
     assert b.survey_bytes_per_env_step(2, 4, 3, 2, True, obs_elem=1) == 536 - 3 * 2 * (23 + 3 + 4)
 
 
+def test_bench_plain_run_times_exactly_steps_and_dumps_a_fixed_sample(tmp_path):
+    """A plain run times --steps steps once and measures nothing beyond the headline (--full adds it);
+    --dump-outputs writes float32 / float64 arrays, within its byte budget the same seeded sample of
+    envs for every array."""
+    import torch
+    b = _load_bench()
+    a = b.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.reps == 1 and not a.full and a.dump_outputs is None
+    a = b.parse(["--steps", "20", "--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    n = 1000
+    outs = {"obs": torch.arange(2 * 3 * n, dtype=torch.int32).view(2, 3, n) % n,
+            "timestep": torch.arange(n, dtype=torch.float64) / 7, "done": torch.arange(n, dtype=torch.int32) % 2,
+            "rows8": (torch.arange(n) % 100).to(torch.int8)}
+    assert b.dump_outputs(outs, str(tmp_path / "all")) == {"obs": [2, 3, n], "timestep": [n], "done": [n], "rows8": [n]}
+    for k, v in outs.items():
+        got = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert got.dtype == (np.float64 if k == "timestep" else np.float32)
+        assert np.array_equal(got, v.numpy())
+    full_bytes = 4 * (6 * n) + 8 * n + 4 * n + 4 * n
+    shapes = b.dump_outputs(outs, str(tmp_path / "s1"), limit=full_bytes // 4)
+    b.dump_outputs(outs, str(tmp_path / "s2"), limit=full_bytes // 4)
+    m = shapes["done"][0]
+    assert 0 < m <= n // 4 and shapes["obs"] == [2, 3, m]
+    got = {k: np.load(str(tmp_path / "s1" / (k + ".npy"))) for k in outs}
+    assert sum(x.nbytes for x in got.values()) <= full_bytes // 4
+    idx = got["obs"][0, 0].astype(np.int64)                 # obs[0][0][e] == e: the sampled env indices
+    assert (np.diff(idx) > 0).all()
+    assert np.array_equal(got["timestep"], outs["timestep"].numpy()[idx])
+    assert np.array_equal(got["done"], outs["done"].numpy()[idx].astype(np.float32))
+    for k in outs:                                          # seeded: the same sample every time
+        assert np.array_equal(got[k], np.load(str(tmp_path / "s2" / (k + ".npy"))))
+
+
 def test_bench_never_reports_one_gpu_for_an_n_gpu_request(monkeypatch, capsys):
     """`python bench.py --gpus N` without a launcher starts N ranks through torch.distributed.run
     and relays rank 0's line ONLY if it says n_gpus == N (VERDICT r1 / ADVICE r1)."""

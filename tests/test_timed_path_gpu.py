@@ -197,6 +197,39 @@ def test_bench_self_spawned_two_ranks_gloo_same_gpu():
     assert j["timing"]["value_from"].startswith("barrier-bracketed wall")
 
 
+def test_bench_plain_run_dumps_its_last_step_reproducibly(tmp_path, oracle_lib):
+    """A plain ``bench.py --steps K`` times exactly K steps, and ``--dump-outputs`` writes what the last
+    of them returned: identical in two runs whose untimed settle differs, and equal to the oracle
+    stepped from reset over the first K actions of the seeded window the timed region replays."""
+    K, n, C = 50, 4096, 2
+    runs = []
+    for settle in ("0", "30"):
+        d = tmp_path / ("settle" + settle)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "5",
+               "--settle-ms", settle, "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, env=_child_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+        j = _last_json(out.stdout)
+        assert j["steps"] == K and j["reps"] == 1 and j["rollout_metrics"]["env_steps"] == n * K
+        assert j["cpu_baseline"] == {"skipped": "measured with --full"} and j["ms_per_step"] > 0
+        runs.append({k: np.load(str(d / (k + ".npy"))) for k in ("obs", "timestep", "shaped_reward", "done")})
+    for k in runs[0]:
+        assert runs[0][k].dtype == (np.float64 if k in ("timestep", "shaped_reward") else np.float32), k
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    b = _bench()
+    from gym_comm_amd import dist as ocdist
+    args = b.parse(["--steps", str(K)])
+    env, _, acts = b.open_loop_workload(args, torch.device("cuda", 0), ocdist.rank_seed(args.seed, 0))
+    ora = oracle_lib.OracleBatch(env.level.blob, n)
+    comm = np.zeros((2, n), np.int32)
+    for k in range(K):
+        oo, to, ro, do = ora.multi_step(acts[k].cpu().numpy(), comm, 2, 0, C, auto_reset=True)
+    got = runs[0]
+    assert np.array_equal(got["obs"], oo.astype(np.float32))
+    assert np.array_equal(bits(got["timestep"]), bits(to)) and np.array_equal(bits(got["shaped_reward"]), bits(ro))
+    assert np.array_equal(got["done"], do.astype(np.float32))
+
+
 def test_timeline_build_records_every_launch_and_steps_identically():
     """The -DOC_TIMELINE flavour behind ``bench.py --decompose`` (include/oc_hip.h: oc_timeline_begin):
     same results as the product build, one record per launch with every wave counted and

@@ -4,7 +4,7 @@
 TAG="$1"; OUT=gpurun_out/bench_$TAG; mkdir -p $OUT
 cd "$(dirname "$0")/.."
 b() { name=$1; shift; python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.log || echo "FAILED $name"; echo "$name $(python -c "import json,sys; d=json.loads(open('$OUT/$name.json').read()); print('%.3f us/step' % (d['ms_per_step']*1e3), '%.3g' % d['value'], d['unit'], 'frac', d.get('roofline',{}).get('frac'))" 2>/dev/null)"; }
-b open-divider_tomato_4096                                   # the default: BASELINE configs[1], with cpu_baseline
+b open-divider_tomato_4096 --full                            # the default: BASELINE configs[1], with cpu_baseline
 b tomato_4096_steps20 --steps 20 --warmup 5 --no-cpu-baseline    # the driver's form
 b tomato_4096_steps20000 --steps 20000 --no-cpu-baseline
 b tomato_4096_one_wave --waves-per-64 1 --no-cpu-baseline        # the launch the split replaced
