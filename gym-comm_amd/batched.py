@@ -157,7 +157,7 @@ class BatchedOvercooked:
         """The wrapper configuration of the reference's own run files (communication on, not ego-led,
         both players CAN_MOVE, ego = sim agent 0, nobody BLIND, play off): what the plain step and
         the options-on-the-standard-configuration variant of the fused kernel fold at compile time
-        (csrc/oc_kernels.hip: XO = 0 / 1); anything else runs the general variant."""
+        (csrc/oc_kernels.hip: MultiVariant, xo = 0 / 1); anything else runs the general variant."""
         c = self._wrap_cfg
         return bool(c.communication_on and not c.ego_led and c.can_move_mask == 3 and c.ego_agent_idx == 0
                     and c.obs.blind_mask == 0 and not self.level.play)

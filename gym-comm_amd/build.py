@@ -11,7 +11,10 @@ import subprocess
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SOURCES = ["oc_kernels.hip"]
 HEADERS = ["oc_hip.h", "oc_level.h"]          # include/: what SOURCES include
-LOCAL_HEADERS = ["oc_policy_device.h"]        # csrc/: the policy's device code, shared with POLICY_SOURCES
+# csrc/: the policy's device code, included by SOURCES and by POLICY_SOURCES ...
+POLICY_LOCAL_HEADERS = ["oc_policy_device.h"]
+# ... and the stepper's host half and its kernels, both included by oc_kernels.hip alone
+LOCAL_HEADERS = ["oc_level_host.h", "oc_step_device.h"] + POLICY_LOCAL_HEADERS
 LIB = os.path.join(CSRC, "liboc_hip.so")
 # the policy library (include/oc_policy.h): its own translation unit and shared object, so that
 # the stepper's specialised builds neither contain nor depend on it
@@ -75,7 +78,7 @@ def build(force=False, verbose=False, extra_flags=()):
 
 def build_policy(force=False, verbose=False):
     """Compile the MLP policy kernel (include/oc_policy.h) into csrc/liboc_policy.so."""
-    if not force and not needs_build(POLICY_LIB, POLICY_SOURCES, POLICY_HEADERS, LOCAL_HEADERS):
+    if not force and not needs_build(POLICY_LIB, POLICY_SOURCES, POLICY_HEADERS, POLICY_LOCAL_HEADERS):
         return POLICY_LIB
     return _compile(POLICY_LIB, POLICY_SOURCES, POLICY_FLAGS, verbose)
 

@@ -390,7 +390,7 @@ def test_env_args_json_loader(tmp_path):
 
 
 def test_two_fma_timestep_quotient_equals_division_exhaustively(tmp_path):
-    """timestep_of() in oc_kernels.hip forms t / T (overcooked_env.py:146) as
+    """timestep_of() in oc_step_device.h forms t / T (overcooked_env.py:146) as
     t * RN(1/T) + one FMA residual + one FMA correction instead of an fp64 division.
     tools/div_check.c compares it with the correctly rounded quotient, bit for bit, for
     every 0 <= t <= 65535 and 1 <= T <= 65535 (the ranges the 16-bit fields allow)."""
@@ -399,6 +399,42 @@ def test_two_fma_timestep_quotient_equals_division_exhaustively(tmp_path):
                            "-o", exe, "-lm"])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300, check=True).stdout
     assert "mismatches: 0" in out, out
+
+
+def test_level_host_header_alone(tmp_path):
+    """gym-comm_amd/csrc/oc_level_host.h -- the blob compiler (with its restatement of CPython's set
+    order and its stable insertion sort over raw blob words), the generator of the specialised
+    header and the hand-sized table image -- is plain host C++: tests/host_header_driver.cc includes
+    nothing else of the stepper and is compiled by the host compiler with the address and
+    undefined-behaviour sanitizers.  For the blob of every built-in level at every agent count it
+    supports, the text the driver emits for both flavours of library equals what liboc_hip.so's
+    oc_level_spec_source returns, and the sanitizers report nothing."""
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    from gym_comm_amd import build, compiler, specialize
+    from gym_comm_amd import levels as L
+    build.build()
+    exe = str(tmp_path / "host_header_driver")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "host_header_driver.cc"),
+                           "-o", exe])
+    # (ASan otherwise insists on being the first library of the process, whatever the environment preloads)
+    env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0")
+    cases = 0
+    for name in sorted(L.BUILTIN):
+        for agents in range(2, min(4, len(L.load_level(name).agent_starts)) + 1):
+            lv = compiler.compile_level(name, agents, 500)
+            blob = tmp_path / ("%s_a%d.blob" % (name, agents))
+            np.ascontiguousarray(lv.blob, dtype=np.int32).tofile(str(blob))
+            for geometry in (True, False):
+                out = subprocess.run([exe, str(blob), "1" if geometry else "0"], capture_output=True, text=True,
+                                     env=env, timeout=120)
+                assert out.returncode == 0 and out.stderr == "", (name, agents, geometry, out.returncode, out.stderr)
+                assert out.stdout == specialize.spec_header_text(lv.blob, geometry), (name, agents, geometry)
+                cases += 1
+    assert cases >= 2 * 2 * len(L.BUILTIN)
 
 
 def test_no_kernel_spills_to_scratch(tmp_path):

@@ -1,5 +1,5 @@
 // Exhaustive check (4.3e9 pairs, ~6 s): the two-FMA quotient used by timestep_of() in
-// gym-comm_amd/csrc/oc_kernels.hip equals the correctly rounded fp64 division t / T for every
+// gym-comm_amd/csrc/oc_step_device.h equals the correctly rounded fp64 division t / T for every
 // 0 <= t <= 65535, 1 <= T <= 65535.   gcc -O2 -ffp-contract=off tools/div_check.c -lm
 #include <math.h>
 #include <stdio.h>

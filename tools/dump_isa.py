@@ -2,13 +2,19 @@
 """Device assembly of a level's specialised kernels + static instruction statistics per kernel.
 
     python tools/dump_isa.py open-divider_tomato 2 [--out /tmp/k.s] [--variant timeline]
-                             [--structure] [--match k_multi_step] [--flags "-DX ..."]
+                             [--structure] [--match k_multi_step] [--flags "-DX ..."] [--digest]
 
-Compiles csrc/oc_kernels.hip exactly as specialize.ensure() would (-S --cuda-device-only instead
+Compiles csrc/oc_kernels.hip (with the two headers it includes) exactly as specialize.ensure() would (-S --cuda-device-only instead
 of -shared) and prints, for every kernel whose demangled name matches: VGPRs / SGPRs / scratch and
 the static count of VALU / SALU / VMEM / SMEM / LDS / waitcnt / branch instructions.  Static counts of a
-split kernel cover all arms; per-arm figures come from the `; %bb` ranges (use --arms)."""
+split kernel cover all arms; per-arm figures come from the `; %bb` ranges (use --arms).
+
+--digest prints, for EVERY kernel, one line "<sha256 of its instruction stream and .amdhsa_*
+descriptor block> <number of lines hashed>  <demangled name>", sorted by name: run it in two source trees and `diff` the
+outputs to see whether a change touched any device code (comments, the per-build __hip_cuid_*
+symbol and the .ident line do not enter the digest)."""
 import argparse
+import hashlib
 import os
 import re
 import subprocess
@@ -38,6 +44,22 @@ def classify(op):
     return "OTHER"
 
 
+def kernel_digest(body):
+    """sha256 over a kernel's labels + instructions and its .amdhsa_kernel descriptor block,
+    comments and every other directive stripped (branch labels stay, without the index of the
+    function in the module: .LBB<fn>_<n>, which only says in which order kernels were emitted)"""
+    lines = []
+    code, _, rest = body.partition(".amdhsa_kernel")
+    for ln in code.splitlines():
+        ln = re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";")[0].strip())
+        if ln and (ln.startswith(".LBB_") or not ln.startswith(".")):
+            lines.append(ln)
+    for ln in rest.split(".end_amdhsa_kernel")[0].splitlines()[1:]:
+        if ln.strip().startswith(".amdhsa_"):
+            lines.append(" ".join(ln.split()))
+    return hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16], len(lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("level")
@@ -48,6 +70,7 @@ def main():
     ap.add_argument("--generic", action="store_true")
     ap.add_argument("--match", default="k_multi_step|k_step")
     ap.add_argument("--flags", default="")
+    ap.add_argument("--digest", action="store_true")
     a = ap.parse_args()
     from gym_comm_amd import build, compiler, specialize
     lv = compiler.compile_level(a.level, a.agents, 500)
@@ -65,6 +88,16 @@ def main():
     # kernels: "<mangled>:" ... ".end_amdhsa_kernel" / s_endpgm region; split on .globl
     parts = re.split(r"\n\t\.globl\t(\S+)", text)
     rx = re.compile(a.match)
+    if a.digest:
+        rows = []
+        for k in range(1, len(parts), 2):
+            if ".amdhsa_kernel" not in parts[k + 1]:
+                continue
+            dem = subprocess.run(["c++filt", parts[k]], capture_output=True, text=True).stdout.strip()
+            rows.append("%s %5d  %s" % (*kernel_digest(parts[k + 1]), dem))
+        print("\n".join(sorted(rows, key=lambda r: r.split("  ", 1)[1])))
+        print("kernels:", len(rows))
+        return
     for k in range(1, len(parts), 2):
         name, body = parts[k], parts[k + 1]
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
