@@ -340,6 +340,47 @@ struct RowsT {
     typedef int v2i __attribute__((ext_vector_type(2)));
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i, v), rsrc, voff, row * rowbytes, AUX);
   }
+  // a run of rows stored from a loop: the caller carries the row's byte offset along (soff(first
+  // row), += rowbytes per row) instead of multiplying for every row
+  __device__ __forceinline__ int soff(int row) const { return row * rowbytes; }
+  __device__ __forceinline__ void st_at(int so, int, int v) const {
+    __builtin_amdgcn_raw_buffer_store_b32(v, rsrc, voff, so, AUX);
+  }
+  __device__ __forceinline__ void st8_at(int so, int, int v) const {
+    __builtin_amdgcn_raw_buffer_store_b8((char)v, rsrc, voff, so, AUX);
+  }
+};
+// One viewer's rows of the observation tensor with the byte offsets of its first N rows held in
+// SGPRs: so[k] = (row0 + k) * rowbytes.  The caller forms them (a chain of adds) where it has
+// nothing else to do -- a split workgroup's observation waves, under the wait for the state in
+// front of the barrier -- so that the ~30 row stores at the end of the step are not each
+// preceded by a scalar multiply: a lone wave pays ~4 cycles for every instruction it issues,
+// whatever its type (tools/issue_probe.hip).  Rows are named as everywhere else, by their index
+// in the tensor; every store of one of the first N rows must name it by a compile-time offset
+// from row0 (straight-line or fully unrolled code), or the table would have to live in memory.
+template <int AUX, int N>
+struct RowsPreT : RowsT<AUX> {   // (N == 0: no table, a plain RowsT)
+  int so[N > 0 ? N : 1];
+  int row0;
+  __device__ __forceinline__ RowsPreT(const RowsT<AUX> &rows, int row0_) : RowsT<AUX>(rows), row0(row0_) {
+    [[maybe_unused]] int o = row0_ * rows.rowbytes;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+      so[k] = o;
+      asm volatile("" : "+s"(so[k]));   // formed HERE, held until its store
+      o = so[k] + rows.rowbytes;
+    }
+  }
+  __device__ __forceinline__ int off(int row) const {
+    const int k = row - row0;
+    return (k >= 0 && k < N) ? so[k] : row * this->rowbytes;
+  }
+  __device__ __forceinline__ void st(int row, int v) const {
+    __builtin_amdgcn_raw_buffer_store_b32(v, this->rsrc, this->voff, off(row), AUX);
+  }
+  __device__ __forceinline__ void st8(int row, int v) const {
+    __builtin_amdgcn_raw_buffer_store_b8((char)v, this->rsrc, this->voff, off(row), AUX);
+  }
 };
 // RowsT that also leaves every stored value, as a float, in an LDS image [row - rowbase][64 lanes]:
 // how a split workgroup's observation waves hand a viewer's rows to the waves that evaluate the
@@ -356,6 +397,14 @@ struct RowsLdsT : RowsT<AUX> {
   }
   __device__ __forceinline__ void st8(int row, int v) const {
     RowsT<AUX>::st8(row, v);
+    lds[(row - rowbase) * 64 + lane] = (float)v;
+  }
+  __device__ __forceinline__ void st_at(int so, int row, int v) const {
+    RowsT<AUX>::st_at(so, row, v);
+    lds[(row - rowbase) * 64 + lane] = OT == 2 ? __builtin_bit_cast(float, v) : (float)v;
+  }
+  __device__ __forceinline__ void st8_at(int so, int row, int v) const {
+    RowsT<AUX>::st8_at(so, row, v);
     lds[(row - rowbase) * 64 + lane] = (float)v;
   }
 };
@@ -983,10 +1032,34 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
 // writes F = 22 + S + 2C rows with stride n.
 // OT = element type of the observation rows: 0 int32, 1 int8, 2 float32 (the same integers,
 // converted; what a policy network's first layer consumes as obs[v].T without a cast)
+// The bit of `completed` that each completed_subtasks row shows (RunCfg::slot4), one scalar per
+// row: it depends on the launch alone, so a caller with idle time before its stores forms it there
+// (multi_step_body: in front of the barrier) and the rows themselves are one bit-field extract each,
+// with no test of slot_identity among the stores.  Specialised builds only (S is a constant).
+#ifdef OC_SPECIALIZED
+constexpr int OBS_NSLOT = OC_SPEC_HDR.S > 0 ? OC_SPEC_HDR.S : 1;
+#else
+constexpr int OBS_NSLOT = 1;
+#endif
+struct ObsSlots {
+  int sh[OBS_NSLOT];
+  __device__ __forceinline__ ObsSlots(const RunCfg &R, bool pin) {
+#ifdef OC_SPECIALIZED
+#pragma unroll
+    for (int s = 0; s < (int)OC_SPEC_HDR.S; s++) {
+      sh[s] = R.slot_identity ? s : (int)((R.slot4[s >> 2] >> (8 * (s & 3))) & 31);   // uniform
+      if (pin) asm volatile("" : "+s"(sh[s]));
+    }
+#else
+    sh[0] = 0;
+#endif
+  }
+};
+
 template <int A, int M, bool DUP, int OT, typename OutRows>
-__device__ __forceinline__ void env_obs(const Hdr &L, const RunCfg &R, const Env<A, M, DUP> &e, int viewer, int radius,
-                                        bool viewer_blind, bool ego_blind, int C, int comm0, int comm1,
-                                        const OutRows &out, int row0) {
+__device__ __forceinline__ void env_obs(const Hdr &L, const RunCfg &R, const ObsSlots &slots, const Env<A, M, DUP> &e,
+                                        int viewer, int radius, bool viewer_blind, bool ego_blind, int C, int comm0,
+                                        int comm1, const OutRows &out, int row0) {
   const int vp = viewer == 0 ? e.ap[0] : e.ap[1];
   const int vhp = viewer == 0 ? e.ahp[0] : e.ahp[1];
   const int vx = px(vp), vy = py(vp);
@@ -1033,24 +1106,59 @@ __device__ __forceinline__ void env_obs(const Hdr &L, const RunCfg &R, const Env
   for (int ch = 0; ch < 4; ch++) OUT(row++, st[ch]);
 #pragma unroll
   for (int ch = 0; ch < 4; ch++) OUT(row++, hid[ch]);
-  if (R.slot_identity) {   // uniform: the caller's order is the canonical one
-    for (int s = 0; s < L.S(); s++) OUT(row++, (e.completed >> s) & 1);
-  } else {
-    for (int s = 0; s < L.S(); s++) OUT(row++, (e.completed >> ((R.slot4[s >> 2] >> (8 * (s & 3))) & 31)) & 1);
+  // (a run of rows whose number is only known at run time: the byte offset is carried along)
+#define OUT_AT(so_, r_, v_)                                                            \
+  do {                                                                                 \
+    if (OT == 1) out.st8_at((so_), (r_), (v_));                                        \
+    else if (OT == 2) out.st_at((so_), (r_), __builtin_bit_cast(int, (float)(v_)));    \
+    else out.st_at((so_), (r_), (v_));                                                 \
+  } while (0)
+#ifdef OC_SPECIALIZED
+#pragma unroll
+  for (int s = 0; s < (int)OC_SPEC_HDR.S; s++) OUT(row++, (e.completed >> slots.sh[s]) & 1);
+#else
+  {
+    int so = out.soff(row);
+    if (R.slot_identity) {   // uniform: the caller's order is the canonical one
+      for (int s = 0; s < L.S(); s++, row++, so += out.rowbytes) OUT_AT(so, row, (e.completed >> s) & 1);
+    } else {
+      for (int s = 0; s < L.S(); s++, row++, so += out.rowbytes)
+        OUT_AT(so, row, (e.completed >> ((R.slot4[s >> 2] >> (8 * (s & 3))) & 31)) & 1);
+    }
   }
+#endif
 #pragma unroll
   for (int k = 0; k < 4; k++) OUT(row++, loc[k]);
   OUT(row++, ego_blind ? 0 : (vhp != 0 ? 1 : 0));  // :154, gated on the EGO's BLIND flag
   OUT(row++, 0);
-  if (C == 2) {  // uniform; the BASELINE configuration: straight-line instead of four scalar loops
-    OUT(row++, comm0 == 0 ? 1 : 0);
-    OUT(row++, comm0 == 1 ? 1 : 0);
-    OUT(row++, comm1 == 0 ? 1 : 0);
-    OUT(row++, comm1 == 1 ? 1 : 0);
+  // comm one-hots: straight-line for up to four channels (uniform switch; the BASELINE
+  // configuration has two), a loop beyond.  (Every case ends on an empty asm statement: the
+  // optimiser otherwise merges the cases' last stores into one shared tail and pays for it with
+  // a dozen flag moves and branches -- inline asm is never sunk into a common successor.)
+#define COMM_ROWS(CC_)                                                     \
+  do {                                                                     \
+    _Pragma("unroll") for (int c = 0; c < (CC_); c++) OUT(row + c, comm0 == c ? 1 : 0);          \
+    _Pragma("unroll") for (int c = 0; c < (CC_); c++) OUT(row + (CC_) + c, comm1 == c ? 1 : 0);  \
+    asm volatile("");                                                                            \
+  } while (0)
+  if (C == 2) {   // the BASELINE configuration first: one compare and one branch ...
+    COMM_ROWS(2);
   } else {
-    for (int c = 0; c < C; c++) OUT(row++, comm0 == c ? 1 : 0);
-    for (int c = 0; c < C; c++) OUT(row++, comm1 == c ? 1 : 0);
+    int Cx = C;
+    asm("" : "+s"(Cx));   // (... which the optimiser would otherwise fold back into the switch)
+    switch (Cx) {
+      case 1: COMM_ROWS(1); break;
+      case 3: COMM_ROWS(3); break;
+      case 4: COMM_ROWS(4); break;
+      default: {
+        int so = out.soff(row);
+        for (int c = 0; c < C; c++, row++, so += out.rowbytes) OUT_AT(so, row, comm0 == c ? 1 : 0);
+        for (int c = 0; c < C; c++, row++, so += out.rowbytes) OUT_AT(so, row, comm1 == c ? 1 : 0);
+      }
+    }
   }
+#undef COMM_ROWS
+#undef OUT_AT
 #undef OUT
 }
 
@@ -1373,9 +1481,10 @@ __global__ void __launch_bounds__(256) k_obs(const ObsArgs p) {
   const int c0 = p.comm[i], c1 = p.comm[p.n + i];
   const bool ego_blind = p.cfg.blind_mask & 1;
   const Out ob(p.obs, p.n, 2 * F, i, OT == 1 ? 1 : 4);
+  const ObsSlots slots(p.R, false);
 #pragma unroll
   for (int v = 0; v < 2; v++)
-    env_obs<A, M, DUP, OT>(L, p.R, e, v, p.cfg.fow_radius, (p.cfg.blind_mask >> v) & 1, ego_blind, C, c0, c1, ob, v * F);
+    env_obs<A, M, DUP, OT>(L, p.R, slots, e, v, p.cfg.fow_radius, (p.cfg.blind_mask >> v) & 1, ego_blind, C, c0, c1, ob, v * F);
   Out(p.timestep, p.n, 1, i, 8).st_f64(0, timestep_of(e.t, p.R));  // overcooked_env.py:146
 }
 
@@ -1732,6 +1841,29 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     }
     Env<A, M, DUP> e;
     unpack<A, M, DUP>(e, w);
+    // What the observation rows need of the LAUNCH alone -- the descriptor of the tensor, which
+    // bit of `completed` each subtask row shows and, in a split workgroup's observation waves, the
+    // byte offset of every row the wave will store -- is formed here, under the wait for the state:
+    // the ~30 row stores are the tail of the step's longest waves, and every scalar instruction
+    // among them costs a lone wave its ~4 cycles.
+    const int C = p.cfg.obs.num_comm;
+    const int F = 22 + L.S() + 2 * C;
+    const Out ob(p.obs, p.n, 2 * F, i, OT == 1 ? 1 : 4);
+    constexpr bool OBS_ONLY = SPLIT && (DUTY == DUTY_OBS0 || DUTY == DUTY_OBS1);
+#ifdef OC_SPECIALIZED
+    // (the plain variant only, and at most 40 offsets -- salad's 22 + 9 + 8 fit beside the step's own
+    // ~64 SGPRs; the options variants and a level with more subtasks began to spill SGPRs to VGPR
+    // lanes.  Rows past the table are stored as before, with a multiply.)
+    constexpr int NPRE_ALL = 22 + (int)OC_SPEC_HDR.S + 8;   // up to four comm channels
+    constexpr int NPRE = (OBS_ONLY && !POL && XO == 0) ? (NPRE_ALL < 40 ? NPRE_ALL : 40) : 0;
+#else
+    constexpr int NPRE = 0;   // (the number of subtask rows is a run-time value)
+#endif
+    const ObsSlots slots(p.R, NPRE != 0);
+    const RowsPreT<WT ? AUX_WT : 0, NPRE> obp(ob, DUTY == DUTY_OBS1 ? F : 0);
+    if constexpr (NPRE != 0) asm volatile("" ::"s"(ob.rsrc));   // (the descriptor's words as well)
+    const Out tso(p.timestep, p.n, 1, i, 8);
+    if constexpr (NPRE != 0 && DUTY == DUTY_OBS0) asm volatile("" ::"s"(tso.rsrc), "v"(tso.voff));
     // split: nothing that is updated in place -- state rows, the words of the random streams, the
     // done row the episode statistics read -- may be stored before every wave of the workgroup
     // holds its copy
@@ -1743,6 +1875,10 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
       if constexpr (XO != 0)
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" : "+v"(eq), "+v"(aq), "+v"(er), "+v"(ar), "+v"(alt_rs)::"memory");
       else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+      // (the offsets pinned above hang on scalar loads, and this statement is ordered behind their
+      // pins: left alone, the scheduler fills that latency with the step's arithmetic and the
+      // barrier sinks ~400 instructions, to where the first store needs it)
+      if constexpr (NPRE != 0) __builtin_amdgcn_sched_barrier(0);
     } else if constexpr (XO != 0) {
       asm volatile("" : "+v"(eq), "+v"(aq), "+v"(er), "+v"(ar), "+v"(alt_rs));
     }
@@ -1821,6 +1957,21 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
         const P fresh = -done & p_of(p.auto_reset != 0);
 #pragma unroll
         for (int r = 0; r < WS; r++) w[r] = sel(fresh, L.init_words(r), w[r]);
+      } else if (OBS_ONLY && L.nscatter() == 0) {
+        // an observation wave of a split launch, a fixed level: the same select, on the fields
+        // the observation reads (the rest is dead code here), instead of the branch
+        int32_t w0[WS];
+#pragma unroll
+        for (int r = 0; r < WS; r++) w0[r] = L.init_words(r);
+        Env<A, M, DUP> e0;
+        unpack<A, M, DUP>(e0, w0);
+        const P fresh = -done & p_of(p.auto_reset != 0);
+#pragma unroll
+        for (int a = 0; a < A; a++) e.ap[a] = sel(fresh, e0.ap[a], e.ap[a]), e.ahp[a] = sel(fresh, e0.ahp[a], e.ahp[a]);
+#pragma unroll
+        for (int k = 0; k < M; k++) e.iw[k] = sel(fresh, e0.iw[k], e.iw[k]);
+        e.t = sel(fresh, e0.t, e.t);
+        e.completed = sel(fresh, e0.completed, e.completed);
       } else if (done && p.auto_reset) {
 #pragma unroll
         for (int r = 0; r < WS; r++) w[r] = L.init_words(r);
@@ -1841,30 +1992,28 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     }
     ShapeQ<2> sq;
     if constexpr (D_SHAPE) shaping_lookup<2>(L, p.R.inv_max_path, sin, sld, sq OC_STAMP_PASS);
-    const int C = p.cfg.obs.num_comm;
-    const int F = 22 + L.S() + 2 * C;
     const bool ego_blind = cfg_blind & 1;
-    const Out ob(p.obs, p.n, 2 * F, i, OT == 1 ? 1 : 4);
     if constexpr (POL && SPLIT) {
       // (split launch with the policies fused: the rows also go to the LDS image the policy passes read)
       const int ln = (int)threadIdx.x & 63;
       if constexpr ((DUTY & DUTY_OBS0) != 0) {
         const RowsLdsT<WT ? AUX_WT : 0, OT> obl(ob, pol_lds_feat<POL_ROWS>(), 0, ln);
-        env_obs<A, M, DUP, OT>(L, p.R, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obl, 0);
+        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obl, 0);
         const double tsd = timestep_of(e.t, p.R);
         Out(p.timestep, p.n, 1, i, 8).st_f64(0, tsd);
         pol_lds_ts()[ln] = (float)tsd;
       }
       if constexpr ((DUTY & DUTY_OBS1) != 0) {
         const RowsLdsT<WT ? AUX_WT : 0, OT> obl(ob, pol_lds_feat<POL_ROWS>() + POL_ROWS * 64, F, ln);
-        env_obs<A, M, DUP, OT>(L, p.R, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obl, F);
+        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obl, F);
       }
     } else {
+      // (obp: the rows with this wave's offsets pre-formed, or plain rows where none were)
       if constexpr ((DUTY & DUTY_OBS0) != 0)
-        env_obs<A, M, DUP, OT>(L, p.R, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, ob, 0);
+        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obp, 0);
       if constexpr ((DUTY & DUTY_OBS1) != 0)
-        env_obs<A, M, DUP, OT>(L, p.R, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, ob, F);
-      if constexpr ((DUTY & DUTY_OBS0) != 0) Out(p.timestep, p.n, 1, i, 8).st_f64(0, timestep_of(e.t, p.R));
+        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obp, F);
+      if constexpr ((DUTY & DUTY_OBS0) != 0) tso.st_f64(0, timestep_of(e.t, p.R));
     }
     OC_STAMP(5);   // observation stores issued
     if constexpr (D_SHAPE) {

@@ -92,6 +92,58 @@ MEMPROBE(m_store_voffset_fresh, "v_add_u32 %0, 64, %0\n buffer_store_dword %0, %
 MEMPROBE(m_store_dword_sc1_valu3, "buffer_store_dword %0, %2, %3, 0 offen sc1\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0", 4)
 MEMPROBE(m_store_dword_sc1_valu7, "buffer_store_dword %0, %2, %3, 0 offen sc1\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0\n v_add_u32 %0, 1, %0", 8)
 
+// MIXED streams around NEW-LINE row stores (profiles/obs_tail_issue_probe.txt): 32 write-through row
+// stores, 16 KiB apart as the rows of a 4 096-env tensor are, each followed by k independent VALU
+// or SALU instructions.  Does the issue of a neighbouring instruction overlap the ~14 cycles a row
+// store occupies, or add to them?  And does a store whose soffset was written by the instruction
+// in front of it cost more than one whose soffset has been sitting in its SGPR since before the
+// stream (s[20..51], set ahead of the first time stamp)?  One asm block: the 32 offsets live in
+// fixed SGPRs the compiler must not touch in between.
+#define OC_SREGS32                                                                                 \
+  "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s32", "s33", \
+  "s34", "s35", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", \
+  "s48", "s49", "s50", "s51", "s60", "s61", "s62", "s63"
+#define MIXPROBE(NAME, BODY, NINSTR)                                                               \
+  __global__ void NAME(unsigned long long *out, int *sink, int seed) {                             \
+    int v = threadIdx.x + seed, off = threadIdx.x * 4, a = seed, b = 1, c = 2, d = 3;              \
+    __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(sink + 1024, 0, 1 << 20, 0x00020000); \
+    unsigned long long t0, t1;                                                                     \
+    asm volatile(".set oc_k, 0\n.rept 32\n s_mov_b32 s[20+oc_k], oc_k*16384\n.set oc_k, oc_k+1\n.endr\n" \
+                 " s_mov_b32 s60, 0\n s_mov_b32 s61, 0\n s_mov_b32 s62, 0\n s_mov_b32 s63, 16384\n"    \
+                 " s_memtime %0\n s_waitcnt lgkmcnt(0)\n"                                          \
+                 ".set oc_k, 0\n.rept 32\n" BODY "\n.set oc_k, oc_k+1\n.endr\n"                    \
+                 " s_memtime %1\n s_waitcnt lgkmcnt(0)\n s_waitcnt vmcnt(0)"                       \
+                 : "=&s"(t0), "=&s"(t1), "+v"(a), "+v"(b), "+v"(c), "+v"(d)                        \
+                 : "v"(v), "v"(off), "s"(r)                                                        \
+                 : "memory", "scc", OC_SREGS32);                                                   \
+    if (threadIdx.x == 0) out[0] = (t1 - t0) * (REPS * LOOPS) / 32;                                \
+    sink[threadIdx.x] = v + a + b + c + d;                                                         \
+  }                                                                                                \
+  static const int NAME##_n = NINSTR;
+// operands: %2 a %3 b %4 c %5 d (VGPRs the adds write); %6 the stored value, %7 the lane offset, %8 the descriptor
+#define OC_ST_EARLY " buffer_store_dword %6, %7, %8, s[20+oc_k] offen sc1\n"
+#define OC_VA " v_add_u32 %2, 1, %2\n"
+#define OC_VB " v_add_u32 %3, 1, %3\n"
+#define OC_VC " v_add_u32 %4, 1, %4\n"
+#define OC_VD " v_add_u32 %5, 1, %5\n"
+#define OC_SA " s_add_i32 s60, s60, 1\n"
+#define OC_SB " s_add_i32 s61, s61, 1\n"
+#define OC_SC " s_add_i32 s62, s62, 1\n"
+#define OC_SD " s_add_i32 s63, s63, 1\n"
+MIXPROBE(x_store_newline, OC_ST_EARLY, 1)
+MIXPROBE(x_store_newline_valu1, OC_ST_EARLY OC_VA, 2)
+MIXPROBE(x_store_newline_valu2, OC_ST_EARLY OC_VA OC_VB, 3)
+MIXPROBE(x_store_newline_valu3, OC_ST_EARLY OC_VA OC_VB OC_VC, 4)
+MIXPROBE(x_store_newline_valu4, OC_ST_EARLY OC_VA OC_VB OC_VC OC_VD, 5)
+MIXPROBE(x_store_newline_salu1, OC_ST_EARLY OC_SA, 2)
+MIXPROBE(x_store_newline_salu2, OC_ST_EARLY OC_SA OC_SB, 3)
+MIXPROBE(x_store_newline_salu3, OC_ST_EARLY OC_SA OC_SB OC_SC, 4)
+MIXPROBE(x_store_newline_salu4, OC_ST_EARLY OC_SA OC_SB OC_SC OC_SD, 5)
+// the same number of instructions as x_store_newline_salu1, but the add WRITES the soffset the store reads
+MIXPROBE(x_store_soffset_fresh, " s_add_i32 s60, s60, 16384\n buffer_store_dword %6, %7, %8, s60 offen sc1", 2)
+// ... and as the kernels formed it until now: row * rowbytes, one multiply in front of every store
+MIXPROBE(x_store_soffset_mul, " s_mul_i32 s61, s63, oc_k\n buffer_store_dword %6, %7, %8, s61 offen sc1", 2)
+
 // the same row stores from FOUR waves of one workgroup at once (one per SIMD of a CU, as a split launch has
 // them): do the four share one address / store pipe?
 __global__ void __launch_bounds__(256) m4_store_rows(unsigned long long *out, int *sink, int seed) {
@@ -176,6 +228,17 @@ int main() {
   RUN(m_store_voffset_fresh);
   RUN(m_store_dword_sc1_valu3);
   RUN(m_store_dword_sc1_valu7);
+  RUN(x_store_newline);
+  RUN(x_store_newline_valu1);
+  RUN(x_store_newline_valu2);
+  RUN(x_store_newline_valu3);
+  RUN(x_store_newline_valu4);
+  RUN(x_store_newline_salu1);
+  RUN(x_store_newline_salu2);
+  RUN(x_store_newline_salu3);
+  RUN(x_store_newline_salu4);
+  RUN(x_store_soffset_fresh);
+  RUN(x_store_soffset_mul);
   for (int waves = 1; waves <= 4; waves++) {
     double best = 1e30;
     for (int r = 0; r < 5; r++) {
