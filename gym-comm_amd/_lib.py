@@ -213,3 +213,42 @@ def load_hostio(path=None):
     L._oc_path = path
     _libs[path] = L
     return L
+
+
+ROLLOUT_ABI_VERSION = 1  # include/oc_rollout.h: OC_ROLLOUT_ABI_VERSION
+ROLLOUT_SYMBOLS = ["oc_rollout_abi_version", "oc_rollout_last_error", "oc_rollout_add", "oc_rollout_add_reward",
+                   "oc_rollout_gae"]
+
+
+class RolloutBuf(ctypes.Structure):
+    """oc_rollout_buf (include/oc_rollout.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "timestep", "actions", "log_probs", "values", "episode_starts", "rewards", "dones",
+                 "pos", "last", "count", "ticket", "advantages", "returns")] + \
+               [("n", ctypes.c_int64), ("T", ctypes.c_int32), ("F", ctypes.c_int32), ("obs_type", ctypes.c_int32)]
+
+
+def load_rollout(path=None):
+    """Load (once) and type liboc_rollout.so (include/oc_rollout.h): the rollout buffer's kernels."""
+    path = os.path.abspath(path or os.environ.get("OC_ROLLOUT_LIB") or _build.ROLLOUT_LIB)
+    if path in _libs:
+        return _libs[path]
+    if not os.path.exists(path):
+        raise OcError(
+            "HIP extension %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
+            " (there is no CPU fallback)" % path)
+    _preload_torch_hip_runtime()
+    L = ctypes.CDLL(path)
+    vp, bp = ctypes.c_void_p, ctypes.POINTER(RolloutBuf)
+    L.oc_rollout_abi_version.restype = ctypes.c_int
+    L.oc_rollout_last_error.restype = ctypes.c_char_p
+    L.oc_rollout_add.argtypes = [bp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.oc_rollout_add_reward.argtypes = [bp, vp, vp, vp]
+    L.oc_rollout_gae.argtypes = [bp, vp, vp, ctypes.c_double, ctypes.c_double, vp]
+    for f in ("oc_rollout_add", "oc_rollout_add_reward", "oc_rollout_gae"):
+        getattr(L, f).restype = ctypes.c_int
+    if L.oc_rollout_abi_version() != ROLLOUT_ABI_VERSION:
+        raise OcError("liboc_rollout.so ABI version mismatch")
+    L._oc_path = path
+    _libs[path] = L
+    return L

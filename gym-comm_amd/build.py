@@ -26,6 +26,12 @@ POLICY_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", 
 HOSTIO_SOURCES = ["oc_hostio.hip"]
 HOSTIO_HEADERS = ["oc_hostio.h"]
 HOSTIO_LIB = os.path.join(CSRC, "liboc_hostio.so")
+# the rollout-buffer library (include/oc_rollout.h): one-launch recording and the GAE kernel, whose
+# float32 chain must reproduce stable-baselines3's operation order bit for bit: no contraction
+ROLLOUT_SOURCES = ["oc_rollout.hip"]
+ROLLOUT_HEADERS = ["oc_rollout.h"]
+ROLLOUT_LIB = os.path.join(CSRC, "liboc_rollout.so")
+ROLLOUT_FLAGS = POLICY_FLAGS + ["-ffp-contract=off", "-fno-fast-math"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
@@ -90,7 +96,15 @@ def build_hostio(force=False, verbose=False):
     return _compile(HOSTIO_LIB, HOSTIO_SOURCES, POLICY_FLAGS, verbose)
 
 
+def build_rollout(force=False, verbose=False):
+    """Compile the rollout buffer's kernels (include/oc_rollout.h) into csrc/liboc_rollout.so."""
+    if not force and not needs_build(ROLLOUT_LIB, ROLLOUT_SOURCES, ROLLOUT_HEADERS, ()):
+        return ROLLOUT_LIB
+    return _compile(ROLLOUT_LIB, ROLLOUT_SOURCES, ROLLOUT_FLAGS, verbose)
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_policy(force=True, verbose=True))
     print(build_hostio(force=True, verbose=True))
+    print(build_rollout(force=True, verbose=True))

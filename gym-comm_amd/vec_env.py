@@ -221,9 +221,16 @@ class RolloutSink:
     Every write is an ``index_copy_`` / ``index_add_`` on that scalar, so recording neither
     synchronises nor changes shape: it can sit inside a captured hipGraph (a learner's hook that runs
     host code per step cannot).  ``full()`` / ``steps()`` read the counter (one sync, when asked);
-    ``reset()`` starts the next rollout.  Past ``n_steps`` the position wraps (a ring)."""
+    ``reset()`` starts the next rollout.  Past ``n_steps`` the position wraps (a ring).
 
-    def __init__(self, n_steps, n, rows, device="cuda", obs_dtype=torch.int32):
+    ``fused=True``: the same tensors and counters, written by ``liboc_rollout.so``
+    (include/oc_rollout.h) -- ONE launch per ``add``, one per ``add_reward`` (about a dozen and four
+    torch launches otherwise), storing the same bits -- plus ``advantages`` / ``returns`` filled by
+    ONE launch of ``compute_returns_and_advantage`` (the third buffer call of agents.py:127-131)."""
+
+    _OBS_TYPE = {torch.int32: 0, torch.int8: 1, torch.float32: 2}      # include/oc_hostio.h: obs_type
+
+    def __init__(self, n_steps, n, rows, device="cuda", obs_dtype=torch.int32, fused=False):
         dev = torch.device(device)
         T = self.n_steps = int(n_steps)
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
@@ -238,8 +245,58 @@ class RolloutSink:
         self.pos = z((1,), torch.int64)                  # next slot
         self.last = z((1,), torch.int64)                 # slot of the most recent add()
         self.count = z((1,), torch.int64)                # adds since reset()
+        self.advantages = self.returns = self.ticket = None
+        self.fused = bool(fused)
+        if self.fused:
+            # one launch per add / add_reward / compute_returns_and_advantage (include/oc_rollout.h)
+            if dev.type != "cuda":
+                raise ValueError("the fused sink's kernels run on the GPU (device=%r); there is no CPU fallback" % (device,))
+            if obs_dtype not in self._OBS_TYPE:
+                raise ValueError("the fused sink stores int32, int8 or float32 rows (got %s)" % (obs_dtype,))
+            self._L = _lib.load_rollout()
+            self.ticket = z((1,), torch.int32)           # the add kernel's workgroup ticket: 0 between calls
+            self.advantages = z((T, n), torch.float32)
+            self.returns = z((T, n), torch.float32)
+            self._dev = dev.index if dev.index is not None else torch.cuda.current_device()
+            self._buf = _lib.RolloutBuf(
+                *[t.data_ptr() for t in (self.obs, self.timestep, self.actions, self.log_probs, self.values,
+                                         self.episode_starts, self.rewards, self.dones, self.pos, self.last,
+                                         self.count, self.ticket, self.advantages, self.returns)],
+                n, T, int(rows), self._OBS_TYPE[obs_dtype])
+
+    def _call(self, name, *args):
+        """One entry point of liboc_rollout.so on the current torch stream of the sink's device."""
+        dev = self._dev
+        with (contextlib.nullcontext() if torch.cuda.current_device() == dev else torch.cuda.device(dev)):
+            rc = getattr(self._L, name)(ctypes.byref(self._buf), *args, torch._C._cuda_getCurrentRawStream(dev))
+        if rc:
+            raise _lib.OcError("%s failed (%d): %s" % (name, rc, self._L.oc_rollout_last_error().decode()))
+
+    @staticmethod
+    def _row(t, dtype, n):
+        """t as the kernel reads it: `dtype`, contiguous, n elements (torch converts what is not)."""
+        if t.dtype != dtype:
+            t = t.to(dtype)
+        t = t.reshape(-1)
+        if t.numel() != n:
+            raise ValueError("a row of %d elements where the sink holds %d envs" % (t.numel(), n))
+        return t if t.is_contiguous() else t.contiguous()
 
     def add(self, rows, timestep, move, comm, log_prob, value, episode_start):
+        if self.fused:
+            n = self.obs.shape[2]
+            if rows.dtype != self.obs.dtype or rows.shape != self.obs.shape[1:]:
+                raise ValueError("rows %s %s where the sink holds %s %s" % (
+                    rows.dtype, tuple(rows.shape), self.obs.dtype, tuple(self.obs.shape[1:])))
+            # converted exactly as the torch path below converts them; what already lies as the kernel
+            # reads it (the env's rows, its action rows, the partner's float32 rows) is passed as it is
+            rows = rows if rows.is_contiguous() else rows.contiguous()
+            keep = (rows, self._row(timestep, torch.float64, n), self._row(move, torch.int32, n),
+                    self._row(comm, torch.int32, n), self._row(log_prob, torch.float32, n),
+                    None if value is None else self._row(value, torch.float32, n),
+                    self._row(episode_start, torch.float32, n))
+            self._call("oc_rollout_add", *[None if t is None else t.data_ptr() for t in keep])
+            return
         i = self.pos
         self.obs.index_copy_(0, i, rows.unsqueeze(0))
         self.timestep.index_copy_(0, i, timestep.unsqueeze(0))
@@ -255,8 +312,53 @@ class RolloutSink:
 
     def add_reward(self, rewards, dones):
         """``update(reward, done)`` of the step the most recent ``add`` belongs to."""
+        if self.fused:
+            n = self.obs.shape[2]
+            keep = (self._row(rewards, torch.float64, n), self._row(dones, torch.int32, n))
+            self._call("oc_rollout_add_reward", keep[0].data_ptr(), keep[1].data_ptr())
+            return
         self.rewards.index_add_(0, self.last, rewards.to(torch.float64).unsqueeze(0))
         self.dones.index_copy_(0, self.last, dones.to(torch.int32).unsqueeze(0))
+
+    def compute_returns_and_advantage(self, last_values, dones, gamma=0.99, gae_lambda=0.95):
+        """stable-baselines3's ``RolloutBuffer.compute_returns_and_advantage`` over the recorded steps
+        (what ``OnPolicyAgent.get_action`` calls on a full buffer before ``train()``, agents.py:127-131):
+        ``last_values`` are the values of the observation after the newest step, ``dones`` whether
+        that step ended its episode.  With L = min(count, n_steps), step k of L lives in slot
+        (pos - L + k) mod n_steps; per env, in float32 and in this order (include/oc_rollout.h):
+
+            delta = ((float)rewards[k] + (g * next_value) * next_non_terminal) - values[k]
+            last  = delta + ((g_lambda * next_non_terminal) * last)
+            advantages[k] = last;  returns[k] = last + values[k]
+
+        Fills and returns ``(advantages, returns)``, float32 [n_steps][n]; slots that hold no step are
+        left as they were.  ``fused=True``: ONE launch, no synchronisation.  Otherwise the loop in
+        torch: a few launches per step and one read of the counters -- slow, and the same bits."""
+        n = self.obs.shape[2]
+        if self.fused:
+            keep = (self._row(last_values, torch.float32, n), self._row(dones, torch.float32, n))
+            self._call("oc_rollout_gae", keep[0].data_ptr(), keep[1].data_ptr(),
+                       ctypes.c_double(float(gamma)), ctypes.c_double(float(gae_lambda)))
+            return self.advantages, self.returns
+        if self.advantages is None:
+            self.advantages = torch.zeros_like(self.values)
+            self.returns = torch.zeros_like(self.values)
+        T = self.n_steps
+        g = float(np.float32(gamma))                                # exact in float32 from here on
+        gl = float(np.float32(float(gamma) * float(gae_lambda)))    # the product in double, as SB3 forms it
+        L, pos = min(self.steps(), T), int(self.pos.item())
+        nv = last_values.reshape(-1).to(torch.float32)
+        nnt = 1.0 - dones.reshape(-1).to(torch.float32)
+        last = torch.zeros_like(nv)
+        for k in range(L - 1, -1, -1):
+            s = (pos - L + k) % T
+            v = self.values[s]
+            delta = (self.rewards[s].to(torch.float32) + (nv * g) * nnt) - v
+            last = delta + ((nnt * gl) * last)
+            self.advantages[s] = last
+            self.returns[s] = last + v
+            nv, nnt = v, 1.0 - self.episode_starts[s]
+        return self.advantages, self.returns
 
     def steps(self):
         return int(self.count.item())
@@ -268,6 +370,8 @@ class RolloutSink:
         self.pos.zero_()
         self.last.zero_()
         self.count.zero_()
+        if self.ticket is not None:
+            self.ticket.zero_()
 
     def get_state(self):
         return self.pos.clone(), self.last.clone(), self.count.clone()
@@ -375,6 +479,16 @@ class RecurrentPolicyPartner:
             self.sink.add_reward(rewards, dones)
         if self.on_update is not None:
             self.on_update(rewards, dones)
+
+    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
+        """What ``OnPolicyAgent.get_action`` does on a full buffer before ``train()`` (agents.py:127-131):
+        ``buf.compute_returns_and_advantage(last_values=self.values, dones=self._last_episode_starts[0])``
+        with the values of the last ``act_into`` and the last ``done`` row.  Returns the sink's
+        (advantages, returns); the sink is NOT reset -- the caller does that after its update
+        (agents.py:158)."""
+        if self.sink is None:
+            raise ValueError("finish_rollout needs a sink")
+        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
 
     def get_state(self, n=None):
         return (tuple(s.clone() for s in self.state), self.episode_start.clone(), self.log_prob.clone(),
