@@ -1,21 +1,19 @@
-"""ctypes loader for liboc_hip.so (include/oc_hip.h) and its per-level specialisations.
+"""ctypes loader for the native libraries: liboc_hip.so (include/oc_hip.h) and its per-level
+specialisations, liboc_policy.so, liboc_hostio.so and liboc_rollout.so.
 
-There is no CPU fallback: if the library cannot be loaded, or a call fails, this
+There is no CPU fallback: if a library cannot be loaded, or a call fails, this
 raises.  (The CPU oracle under oracle/ is test infrastructure and is never used here.)
 """
+import collections
+import contextlib
 import ctypes
 import os
+
+import torch
 
 from . import build as _build
 
 _I32P = ctypes.POINTER(ctypes.c_int32)
-ABI_VERSION = 6          # include/oc_hip.h: OC_ABI_VERSION
-
-SYMBOLS = ["oc_abi_version", "oc_last_error", "oc_level_create", "oc_level_destroy",
-           "oc_level_spec_source", "oc_is_specialized", "oc_level_subtask_info",
-           "oc_metrics_slots", "oc_state_words", "oc_obs_rows", "oc_reset", "oc_step", "oc_obs",
-           "oc_obs_image", "oc_image_words", "oc_multi_step", "oc_multi_step_waves", "oc_random_actions",
-           "oc_timeline_begin", "oc_multi_step_prepare", "oc_call_launch", "oc_call_destroy"]
 
 
 class ObsCfg(ctypes.Structure):
@@ -43,11 +41,6 @@ class StepOpts(ctypes.Structure):
                 ("policy", ctypes.POINTER(StepPolicy))]
 
 
-POLICY_ABI_VERSION = 1   # include/oc_policy.h: OC_POLICY_ABI_VERSION
-POLICY_SYMBOLS = ["oc_policy_abi_version", "oc_policy_last_error", "oc_policy_ksteps", "oc_policy_pack_w1",
-                  "oc_policy_pack_w2", "oc_policy_pack_b2", "oc_policy_mlp"]
-
-
 class PolicyPlayer(ctypes.Structure):
     """oc_policy_player (include/oc_policy.h)."""
     _fields_ = [("obs", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
@@ -55,10 +48,81 @@ class PolicyPlayer(ctypes.Structure):
                 ("logits", ctypes.c_void_p)]
 
 
+class RolloutBuf(ctypes.Structure):
+    """oc_rollout_buf (include/oc_rollout.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "timestep", "actions", "log_probs", "values", "episode_starts", "rewards", "dones",
+                 "pos", "last", "count", "ticket", "advantages", "returns")] + \
+               [("n", ctypes.c_int64), ("T", ctypes.c_int32), ("F", ctypes.c_int32), ("obs_type", ctypes.c_int32)]
+
+
 class OcError(RuntimeError):
     pass
 
 
+# One record per native library (built by build.LIBS[name]): the environment variable that overrides
+# its path, its ABI-version function and the version this loader was written for (the header's
+# OC_*ABI_VERSION), its last-error function, and its prototypes, symbol -> (restype, argtypes);
+# argtypes None = left undeclared (no parameters).
+Lib = collections.namedtuple("Lib", "env abi_fn abi_version last_error protos")
+
+
+def _libs_table():
+    cint, cstr, vp, fp = ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)
+    i32, i64, P = ctypes.c_int32, ctypes.c_int64, ctypes.POINTER
+    bp = P(RolloutBuf)
+    multi_step = [vp, vp, vp, vp, P(WrapCfg), vp, vp, vp, vp, vp, i32, vp, vp, vp, P(StepOpts), i64]
+    return {
+        "hip": Lib("OC_HIP_LIB", "oc_abi_version", 6, "oc_last_error", {
+            "oc_abi_version": (cint, None),
+            "oc_last_error": (cstr, None),
+            "oc_is_specialized": (cint, None),
+            "oc_level_create": (cint, [_I32P, i32, P(vp)]),
+            "oc_level_destroy": (cint, [vp]),
+            "oc_level_spec_source": (cint, [_I32P, i32, i32, cstr, i32]),
+            "oc_level_subtask_info": (cint, [_I32P, i32, _I32P, _I32P, _I32P]),
+            "oc_metrics_slots": (i64, [i64]),
+            "oc_state_words": (i32, [vp]),
+            "oc_obs_rows": (i32, [vp, i32]),
+            "oc_image_words": (i32, [vp]),
+            "oc_reset": (cint, [vp, vp, vp, vp, vp, i64, vp]),
+            "oc_step": (cint, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, vp]),
+            "oc_obs": (cint, [vp, vp, vp, P(ObsCfg), vp, vp, i64, vp]),
+            "oc_obs_image": (cint, [vp, vp, i32, vp, vp, i64, vp]),
+            "oc_multi_step": (cint, multi_step + [vp]),
+            "oc_multi_step_waves": (i32, [i64, i32, i32]),
+            "oc_random_actions": (cint, [vp, vp, vp, i32, i64, vp]),
+            "oc_timeline_begin": (cint, [vp, i64, i64]),
+            "oc_multi_step_prepare": (cint, multi_step + [P(vp)]),
+            "oc_call_launch": (cint, [vp, vp, i32, vp]),
+            "oc_call_destroy": (cint, [vp]),
+        }),
+        "policy": Lib("OC_POLICY_LIB", "oc_policy_abi_version", 1, "oc_policy_last_error", {
+            "oc_policy_abi_version": (cint, None),
+            "oc_policy_last_error": (cstr, None),
+            "oc_policy_ksteps": (i32, [i32]),
+            "oc_policy_pack_w1": (cint, [fp, fp, fp, i32, vp]),
+            "oc_policy_pack_w2": (cint, [fp, i32, vp]),
+            "oc_policy_pack_b2": (cint, [fp, fp, i32, fp]),
+            "oc_policy_mlp": (cint, [P(PolicyPlayer), i32, vp, i32, i32, i32, i64, vp]),
+        }),
+        "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
+            "oc_hostio_abi_version": (cint, None),
+            "oc_hostio_last_error": (cstr, None),
+            "oc_pack_host_bytes": (i64, [i32, i32, i32, i32, i32, i32, i32, i64]),
+            "oc_pack_host": (cint, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+        }),
+        "rollout": Lib("OC_ROLLOUT_LIB", "oc_rollout_abi_version", 1, "oc_rollout_last_error", {
+            "oc_rollout_abi_version": (cint, None),
+            "oc_rollout_last_error": (cstr, None),
+            "oc_rollout_add": (cint, [bp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "oc_rollout_add_reward": (cint, [bp, vp, vp, vp]),
+            "oc_rollout_gae": (cint, [bp, vp, vp, ctypes.c_double, ctypes.c_double, vp]),
+        }),
+    }
+
+
+LIBS = _libs_table()
 _libs = {}
 _hip_preloaded = False
 
@@ -71,58 +135,18 @@ def _preload_torch_hip_runtime():
     global _hip_preloaded
     if _hip_preloaded:
         return
-    import torch
     cand = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
     if os.path.exists(cand):
         ctypes.CDLL(cand, mode=ctypes.RTLD_GLOBAL)
     _hip_preloaded = True
 
 
-def _declare(L):
-    vp = ctypes.c_void_p
-    L.oc_abi_version.restype = ctypes.c_int
-    L.oc_is_specialized.restype = ctypes.c_int
-    L.oc_last_error.restype = ctypes.c_char_p
-    L.oc_level_create.argtypes = [_I32P, ctypes.c_int32, ctypes.POINTER(vp)]
-    L.oc_level_destroy.argtypes = [vp]
-    L.oc_level_spec_source.argtypes = [_I32P, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]
-    L.oc_level_subtask_info.argtypes = [_I32P, ctypes.c_int32, _I32P, _I32P, _I32P]
-    L.oc_metrics_slots.argtypes = [ctypes.c_int64]
-    L.oc_metrics_slots.restype = ctypes.c_int64
-    L.oc_state_words.argtypes = [vp]
-    L.oc_state_words.restype = ctypes.c_int32
-    L.oc_obs_rows.argtypes = [vp, ctypes.c_int32]
-    L.oc_obs_rows.restype = ctypes.c_int32
-    L.oc_image_words.argtypes = [vp]
-    L.oc_image_words.restype = ctypes.c_int32
-    L.oc_reset.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, vp]
-    L.oc_step.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, ctypes.c_int64, vp]
-    L.oc_obs.argtypes = [vp, vp, vp, ctypes.POINTER(ObsCfg), vp, vp, ctypes.c_int64, vp]
-    L.oc_obs_image.argtypes = [vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int64, vp]
-    L.oc_multi_step.argtypes = [vp, vp, vp, vp, ctypes.POINTER(WrapCfg), vp, vp, vp, vp, vp,
-                                ctypes.c_int32, vp, vp, vp, ctypes.POINTER(StepOpts), ctypes.c_int64, vp]
-    L.oc_random_actions.argtypes = [vp, vp, vp, ctypes.c_int32, ctypes.c_int64, vp]
-    L.oc_multi_step_waves.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
-    L.oc_multi_step_waves.restype = ctypes.c_int32
-    L.oc_timeline_begin.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
-    L.oc_multi_step_prepare.argtypes = [vp, vp, vp, vp, ctypes.POINTER(WrapCfg), vp, vp, vp, vp, vp,
-                                        ctypes.c_int32, vp, vp, vp, ctypes.POINTER(StepOpts), ctypes.c_int64,
-                                        ctypes.POINTER(vp)]
-    L.oc_call_launch.argtypes = [vp, vp, ctypes.c_int32, vp]
-    L.oc_call_destroy.argtypes = [vp]
-    for f in ("oc_level_create", "oc_level_destroy", "oc_level_spec_source", "oc_level_subtask_info",
-              "oc_reset", "oc_step",
-              "oc_obs", "oc_obs_image", "oc_multi_step", "oc_random_actions", "oc_timeline_begin",
-              "oc_multi_step_prepare", "oc_call_launch", "oc_call_destroy"):
-        getattr(L, f).restype = ctypes.c_int
-    if L.oc_abi_version() != ABI_VERSION:
-        raise OcError("liboc_hip.so ABI version mismatch")
-    return L
-
-
-def load(path=None):
-    """Load (once per path) and type a library.  Default: the generic liboc_hip.so."""
-    path = os.path.abspath(path or os.environ.get("OC_HIP_LIB") or _build.LIB)
+def load(path=None, lib="hip"):
+    """Load (once per path) and type a library of LIBS.  Default path: the one build.py builds;
+    for "hip" a per-level specialisation's path may be given instead."""
+    rec = LIBS[lib]
+    default = _build.LIBS[lib].lib
+    path = os.path.abspath(path or os.environ.get(rec.env) or default)
     if path in _libs:
         return _libs[path]
     if not os.path.exists(path):
@@ -130,16 +154,49 @@ def load(path=None):
             "HIP extension %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
             " (there is no CPU fallback)" % path)
     _preload_torch_hip_runtime()
-    L = _declare(ctypes.CDLL(path))
+    L = ctypes.CDLL(path)
+    for name, (restype, argtypes) in rec.protos.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
+    if getattr(L, rec.abi_fn)() != rec.abi_version:
+        raise OcError("%s ABI version mismatch" % os.path.basename(default))
+    L._oc_last_error = getattr(L, rec.last_error)
     L._oc_path = path
     _libs[path] = L
     return L
 
 
 def check(rc, what, lib=None):
+    """Raise OcError with the library's own last-error text unless rc is 0."""
     if rc != 0:
-        msg = (lib or load()).oc_last_error()
+        msg = (lib or load())._oc_last_error()
         raise OcError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
+
+
+def raw_stream(dev):
+    """hipStream_t of torch's current stream on device index `dev`, as an int."""
+    try:
+        return torch._C._cuda_getCurrentRawStream(dev)      # ~0.3 us
+    except AttributeError:                                 # older/newer torch
+        return torch.cuda.current_stream(dev).cuda_stream
+
+
+def on_device(dev):
+    """Context in which device index `dev` is current (kernels must be launched with their tensors'
+    device current; one process per GPU is the normal case and costs nothing here)."""
+    if torch.cuda.current_device() == dev:
+        return contextlib.nullcontext()
+    return torch.cuda.device(dev)
+
+
+def call(L, name, dev, *args, stream=True):
+    """Entry point `name` of library L with device `dev` current -- followed, for a launching entry
+    point, by torch's current raw stream on it as the last argument -- and its return code checked."""
+    with on_device(dev):
+        rc = getattr(L, name)(*args, raw_stream(dev)) if stream else getattr(L, name)(*args)
+    check(rc, name, L)
 
 
 def subtask_info(blob, lib=None):
@@ -154,101 +211,3 @@ def subtask_info(blob, lib=None):
     check(L.oc_level_subtask_info(blob.ctypes.data_as(_I32P), int(blob.size), slot.ctypes.data_as(_I32P),
                                   gi.ctypes.data_as(_I32P), ctypes.byref(dup)), "oc_level_subtask_info", L)
     return slot.tolist(), gi.tolist(), bool(dup.value)
-
-
-def load_policy(path=None):
-    """Load (once) and type liboc_policy.so (include/oc_policy.h): the fused MLP policy kernel."""
-    path = os.path.abspath(path or os.environ.get("OC_POLICY_LIB") or _build.POLICY_LIB)
-    if path in _libs:
-        return _libs[path]
-    if not os.path.exists(path):
-        raise OcError(
-            "HIP extension %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no CPU fallback)" % path)
-    _preload_torch_hip_runtime()
-    L = ctypes.CDLL(path)
-    vp, fp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)
-    L.oc_policy_abi_version.restype = ctypes.c_int
-    L.oc_policy_last_error.restype = ctypes.c_char_p
-    L.oc_policy_ksteps.argtypes = [ctypes.c_int32]
-    L.oc_policy_ksteps.restype = ctypes.c_int32
-    L.oc_policy_pack_w1.argtypes = [fp, fp, fp, ctypes.c_int32, vp]
-    L.oc_policy_pack_w2.argtypes = [fp, ctypes.c_int32, vp]
-    L.oc_policy_pack_b2.argtypes = [fp, fp, ctypes.c_int32, fp]
-    L.oc_policy_mlp.argtypes = [ctypes.POINTER(PolicyPlayer), ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32,
-                                ctypes.c_int32, ctypes.c_int64, vp]
-    for f in ("oc_policy_pack_w1", "oc_policy_pack_w2", "oc_policy_pack_b2", "oc_policy_mlp"):
-        getattr(L, f).restype = ctypes.c_int
-    if L.oc_policy_abi_version() != POLICY_ABI_VERSION:
-        raise OcError("liboc_policy.so ABI version mismatch")
-    L._oc_path = path
-    _libs[path] = L
-    return L
-
-
-HOSTIO_ABI_VERSION = 1   # include/oc_hostio.h: OC_HOSTIO_ABI_VERSION
-HOSTIO_SYMBOLS = ["oc_hostio_abi_version", "oc_hostio_last_error", "oc_pack_host_bytes", "oc_pack_host"]
-
-
-def load_hostio(path=None):
-    """Load (once) and type liboc_hostio.so (include/oc_hostio.h): the numpy boundary's pack kernel."""
-    path = os.path.abspath(path or os.environ.get("OC_HOSTIO_LIB") or _build.HOSTIO_LIB)
-    if path in _libs:
-        return _libs[path]
-    if not os.path.exists(path):
-        raise OcError(
-            "HIP extension %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no CPU fallback)" % path)
-    _preload_torch_hip_runtime()
-    L = ctypes.CDLL(path)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    L.oc_hostio_abi_version.restype = ctypes.c_int
-    L.oc_hostio_last_error.restype = ctypes.c_char_p
-    L.oc_pack_host_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32, i64]
-    L.oc_pack_host_bytes.restype = i64
-    L.oc_pack_host.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.oc_pack_host.restype = ctypes.c_int
-    if L.oc_hostio_abi_version() != HOSTIO_ABI_VERSION:
-        raise OcError("liboc_hostio.so ABI version mismatch")
-    L._oc_path = path
-    _libs[path] = L
-    return L
-
-
-ROLLOUT_ABI_VERSION = 1  # include/oc_rollout.h: OC_ROLLOUT_ABI_VERSION
-ROLLOUT_SYMBOLS = ["oc_rollout_abi_version", "oc_rollout_last_error", "oc_rollout_add", "oc_rollout_add_reward",
-                   "oc_rollout_gae"]
-
-
-class RolloutBuf(ctypes.Structure):
-    """oc_rollout_buf (include/oc_rollout.h)."""
-    _fields_ = [(name, ctypes.c_void_p) for name in
-                ("obs", "timestep", "actions", "log_probs", "values", "episode_starts", "rewards", "dones",
-                 "pos", "last", "count", "ticket", "advantages", "returns")] + \
-               [("n", ctypes.c_int64), ("T", ctypes.c_int32), ("F", ctypes.c_int32), ("obs_type", ctypes.c_int32)]
-
-
-def load_rollout(path=None):
-    """Load (once) and type liboc_rollout.so (include/oc_rollout.h): the rollout buffer's kernels."""
-    path = os.path.abspath(path or os.environ.get("OC_ROLLOUT_LIB") or _build.ROLLOUT_LIB)
-    if path in _libs:
-        return _libs[path]
-    if not os.path.exists(path):
-        raise OcError(
-            "HIP extension %s not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
-            " (there is no CPU fallback)" % path)
-    _preload_torch_hip_runtime()
-    L = ctypes.CDLL(path)
-    vp, bp = ctypes.c_void_p, ctypes.POINTER(RolloutBuf)
-    L.oc_rollout_abi_version.restype = ctypes.c_int
-    L.oc_rollout_last_error.restype = ctypes.c_char_p
-    L.oc_rollout_add.argtypes = [bp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.oc_rollout_add_reward.argtypes = [bp, vp, vp, vp]
-    L.oc_rollout_gae.argtypes = [bp, vp, vp, ctypes.c_double, ctypes.c_double, vp]
-    for f in ("oc_rollout_add", "oc_rollout_add_reward", "oc_rollout_gae"):
-        getattr(L, f).restype = ctypes.c_int
-    if L.oc_rollout_abi_version() != ROLLOUT_ABI_VERSION:
-        raise OcError("liboc_rollout.so ABI version mismatch")
-    L._oc_path = path
-    _libs[path] = L
-    return L

@@ -9,8 +9,8 @@ Mirrors, batched:
   gym_comm.envs.OvercookedMultiEnv.multi_step/multi_reset/get_observation2
                                                        (overcooked_env.py:105-297)
 """
-import contextlib
 import ctypes
+import functools
 from typing import Optional
 
 import numpy as np
@@ -22,6 +22,14 @@ from .state import unpack_state
 OBS_KEYS = ["object_encodings_x", "object_encodings_y", "state_encodings", "is_hidden",
             "completed_subtasks", "agent1_location", "agent2_location", "agent_is_holding",
             "agent1_comm", "agent2_comm"]
+# obs_type of the C ABI (include/oc_hip.h, oc_policy.h, oc_hostio.h, oc_rollout.h): the dtype of observation rows
+OBS_TYPE = {torch.int32: 0, torch.int8: 1, torch.float32: 2}
+
+
+def pcg32_seed_states(seed, shape, device="cpu"):
+    """int32 `shape` tensor of seeded PCG32 states (uint32 bit patterns below 2^31) on `device`."""
+    g = torch.Generator(device="cpu").manual_seed(int(seed))
+    return torch.randint(0, 2 ** 31 - 1, tuple(shape), generator=g, dtype=torch.int64).to(torch.int32).to(device)
 
 
 def obs_layout(S, C):
@@ -75,17 +83,18 @@ class BatchedOvercooked:
         blob = np.ascontiguousarray(lv.blob, dtype=np.int32)
         # per-level specialised kernels when available (specialize.py), else the generic library
         self.kernel_flavour, self._L = specialize.load_for(blob, specialize_level)
-        with torch.cuda.device(self.device):
-            h = ctypes.c_void_p()
-            _lib.check(self._L.oc_level_create(blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                               int(blob.size), ctypes.byref(h)), "oc_level_create", self._L)
+        # hipStream_t of torch's current stream on this env's device, as an int
+        self._raw_stream = functools.partial(_lib.raw_stream, self._dev_index)
+        h = ctypes.c_void_p()
+        self._call("oc_level_create", blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(blob.size),
+                   ctypes.byref(h), stream=False)
         self._h = h
         # where the state keeps the bits of subtask s (the library's canonical subtask order)
         self.subtask_slot, self._goal_index, self._dup = _lib.subtask_info(blob, self._L)
         self.W_state = self._L.oc_state_words(h)
         self.F = self._L.oc_obs_rows(h, self.C)
         n = self.n
-        if obs_dtype not in (torch.int32, torch.int8, torch.float32):
+        if obs_dtype not in OBS_TYPE:
             raise ValueError("obs_dtype must be torch.int32, torch.int8 or torch.float32")
         # Every tensor a step reads or writes is a view of ONE device allocation (each view
         # 256-byte aligned): a host consumer fetches the whole step -- state, rewards, done,
@@ -112,7 +121,7 @@ class BatchedOvercooked:
         self._obs_cfg = _lib.ObsCfg(int(fow_radius),
                                     (1 if self.ego_config["BLIND"] else 0) |
                                     (2 if self.partner_config["BLIND"] else 0), self.C,
-                                    {torch.int32: 0, torch.int8: 1, torch.float32: 2}[obs_dtype])
+                                    OBS_TYPE[obs_dtype])
         self._wrap_cfg = _lib.WrapCfg(self._obs_cfg, int(bool(communication_on)), int(bool(ego_led)),
                                       int(ego_agent_idx),
                                       (1 if self.ego_config["CAN_MOVE"] else 0) |
@@ -127,9 +136,7 @@ class BatchedOvercooked:
         self.rng = None
         if lv.random_placement:
             if placement_mode == "rng":
-                g = torch.Generator(device="cpu").manual_seed(int(seed))
-                self.rng = torch.randint(0, 2 ** 31 - 1, (n,), generator=g, dtype=torch.int64
-                                         ).to(torch.int32).to(self.device)
+                self.rng = pcg32_seed_states(seed, (n,), self.device)
             elif placement_mode == "host":
                 nominal = torch.tensor(lv.pack_placement([(x, y) for _, x, y in lv.items]),
                                        dtype=torch.int32)
@@ -171,21 +178,13 @@ class BatchedOvercooked:
 
     # -- helpers ---------------------------------------------------------------
     def _on_device(self):
-        """Kernels must be launched with this env's device current (one process per GPU is
-        the normal case and costs nothing here)."""
-        if torch.cuda.current_device() == self._dev_index:
-            return contextlib.nullcontext()
-        return torch.cuda.device(self.device)
+        """Kernels must be launched with this env's device current."""
+        return _lib.on_device(self._dev_index)
 
-    def _stream(self):
-        return ctypes.c_void_p(self._raw_stream())
-
-    def _raw_stream(self):
-        """hipStream_t of torch's current stream on this env's device, as an int."""
-        try:
-            return torch._C._cuda_getCurrentRawStream(self._dev_index)      # ~0.3 us
-        except AttributeError:                                             # older/newer torch
-            return torch.cuda.current_stream(self.device).cuda_stream
+    def _call(self, name, *args, stream=True):
+        """Entry point `name` of this env's library on its device and torch's current stream (not
+        for the per-step paths below, whose cost is counted in single ctypes calls)."""
+        _lib.call(self._L, name, self._dev_index, *args, stream=stream)
 
     @staticmethod
     def _p(t: Optional[torch.Tensor]):
@@ -205,10 +204,8 @@ class BatchedOvercooked:
         """Reset all envs, or those with mask[n] != 0 (int32 [n])."""
         if mask is not None:
             self._check_tensor(mask, (self.n,), torch.int32, "mask")
-        with self._on_device():
-            _lib.check(self._L.oc_reset(self._h, self._p(self.state), self._p(mask),
-                                        self._p(self.placement), self._p(self.rng), self.n,
-                                        self._stream()), "oc_reset", self._L)
+        self._call("oc_reset", self._h, self._p(self.state), self._p(mask), self._p(self.placement),
+                   self._p(self.rng), self.n)
 
     def set_placement(self, placement: torch.Tensor):
         """placement_mode='host': the start cells (int32 [M][n], x | y<<4, world order) every
@@ -224,20 +221,16 @@ class BatchedOvercooked:
         pre-allocated tensors, overwritten by the next call."""
         self._check_tensor(actions, (self.A, self.n), torch.int32, "actions")
         ar = self.auto_reset if auto_reset is None else auto_reset
-        with self._on_device():
-            _lib.check(self._L.oc_step(self._h, self._p(self.state), self._p(actions),
-                                       self._p(self.reward), self._p(self.done), self._p(self.shaping),
-                                       int(ar), self._p(self.metrics), self._p(self.placement),
-                                       self._p(self.rng), self.n, self._stream()), "oc_step", self._L)
+        self._call("oc_step", self._h, self._p(self.state), self._p(actions), self._p(self.reward),
+                   self._p(self.done), self._p(self.shaping), int(ar), self._p(self.metrics),
+                   self._p(self.placement), self._p(self.rng), self.n)
         return self.reward, self.done, self.shaping
 
     def observe(self):
         """Both viewers' observations of the current state.  Returns (obs int32 [2][F][n],
         timestep f64 [n])."""
-        with self._on_device():
-            _lib.check(self._L.oc_obs(self._h, self._p(self.state), self._p(self.comm),
-                                      ctypes.byref(self._obs_cfg), self._p(self.obs),
-                                      self._p(self.timestep), self.n, self._stream()), "oc_obs", self._L)
+        self._call("oc_obs", self._h, self._p(self.state), self._p(self.comm), ctypes.byref(self._obs_cfg),
+                   self._p(self.obs), self._p(self.timestep), self.n)
         return self.obs, self.timestep
 
     def multi_step(self, actions: Optional[torch.Tensor] = None, auto_reset: Optional[bool] = None,
@@ -320,12 +313,10 @@ class BatchedOvercooked:
         opts = _lib.StepOpts(dp(self.ep_return) or None, dp(self.ep_length) or None, None, alt_pairs_ptr,
                              alt_rng_ptr, alt_played_ptr, 0, self.waves_per_64)
         h = ctypes.c_void_p()
-        with self._on_device():
-            _lib.check(self._L.oc_multi_step_prepare(
-                self._h, dp(self.state), dp(self.comm), actions_ptr or 0, ctypes.byref(self._wrap_cfg), dp(self.obs),
-                dp(self.timestep), dp(self.shaped_reward), dp(self.done), dp(self.reward), int(auto_reset),
-                dp(self.metrics), dp(self.placement), dp(self.rng), ctypes.byref(opts), self.n, ctypes.byref(h)),
-                "oc_multi_step_prepare", self._L)
+        self._call("oc_multi_step_prepare", self._h, dp(self.state), dp(self.comm), actions_ptr or 0,
+                   ctypes.byref(self._wrap_cfg), dp(self.obs), dp(self.timestep), dp(self.shaped_reward),
+                   dp(self.done), dp(self.reward), int(auto_reset), dp(self.metrics), dp(self.placement),
+                   dp(self.rng), ctypes.byref(opts), self.n, ctypes.byref(h), stream=False)
         self._calls = getattr(self, "_calls", [])
         self._calls.append(h)
         L, dev, call = self._L, self._dev_index, h
@@ -354,10 +345,8 @@ class BatchedOvercooked:
             self._image = torch.zeros((2, self._image_words, self.n), dtype=torch.int32, device=self.device)
             self._holding = torch.zeros((2, self.n), dtype=torch.int8, device=self.device)
         r = self._obs_cfg.fow_radius if radius is None else int(radius)
-        with self._on_device():
-            _lib.check(self._L.oc_obs_image(self._h, self._p(self.state), r, self._p(self._image),
-                                            self._p(self._holding), self.n, self._stream()),
-                       "oc_obs_image", self._L)
+        self._call("oc_obs_image", self._h, self._p(self.state), r, self._p(self._image), self._p(self._holding),
+                   self.n)
         if packed:
             return self._image, self._holding
         cells = lv.width * lv.height

@@ -4,35 +4,20 @@ hipcc cross-compiles without a GPU; the built library travels to the GPU box wit
 repo snapshot.  ``-ffp-contract=off``: reward shaping must reproduce CPython's fp64
 arithmetic bit for bit, so no fused multiply-adds may be formed.
 """
+import collections
 import os
 import shutil
 import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+ARCH = "gfx950"
+# the stepper (include/oc_hip.h).  SOURCES / HEADERS / LOCAL_HEADERS / FLAGS are also what the
+# specialised builds compile (specialize.py) and what their cache key hashes
 SOURCES = ["oc_kernels.hip"]
 HEADERS = ["oc_hip.h", "oc_level.h"]          # include/: what SOURCES include
-# csrc/: the policy's device code, included by SOURCES and by POLICY_SOURCES ...
-POLICY_LOCAL_HEADERS = ["oc_policy_device.h"]
-# ... and the stepper's host half and its kernels, both included by oc_kernels.hip alone
-LOCAL_HEADERS = ["oc_level_host.h", "oc_step_device.h"] + POLICY_LOCAL_HEADERS
+# csrc/: the stepper's host half and its kernels, and the policy's device code (shared with oc_policy.hip)
+LOCAL_HEADERS = ["oc_level_host.h", "oc_step_device.h", "oc_policy_device.h"]
 LIB = os.path.join(CSRC, "liboc_hip.so")
-# the policy library (include/oc_policy.h): its own translation unit and shared object, so that
-# the stepper's specialised builds neither contain nor depend on it
-POLICY_SOURCES = ["oc_policy.hip"]
-POLICY_HEADERS = ["oc_policy.h"]
-POLICY_LIB = os.path.join(CSRC, "liboc_policy.so")
-POLICY_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
-# the host-I/O library (include/oc_hostio.h): the numpy boundary's pack-for-PCIe kernel
-HOSTIO_SOURCES = ["oc_hostio.hip"]
-HOSTIO_HEADERS = ["oc_hostio.h"]
-HOSTIO_LIB = os.path.join(CSRC, "liboc_hostio.so")
-# the rollout-buffer library (include/oc_rollout.h): one-launch recording and the GAE kernel, whose
-# float32 chain must reproduce stable-baselines3's operation order bit for bit: no contraction
-ROLLOUT_SOURCES = ["oc_rollout.hip"]
-ROLLOUT_HEADERS = ["oc_rollout.h"]
-ROLLOUT_LIB = os.path.join(CSRC, "liboc_rollout.so")
-ROLLOUT_FLAGS = POLICY_FLAGS + ["-ffp-contract=off", "-fno-fast-math"]
-ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function",
          # leading scalar kernel arguments (k_multi_step) arrive in SGPRs at wave launch
@@ -40,6 +25,23 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fas
 # experiment switches (e.g. OC_HIP_EXTRA_FLAGS=-DOC_TABLES_IN_LDS); they enter the
 # specialisation cache key, so variants never collide
 FLAGS += [f for f in os.environ.get("OC_HIP_EXTRA_FLAGS", "").split() if f]
+_PLAIN_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
+
+Lib = collections.namedtuple("Lib", "sources headers local_headers flags lib")
+# one record per shared object: sources and local headers under csrc/, public headers under include/
+LIBS = {
+    "hip": Lib(SOURCES, HEADERS, LOCAL_HEADERS, FLAGS, LIB),
+    # the policy library (include/oc_policy.h): its own translation unit and shared object, so that
+    # the stepper's specialised builds neither contain nor depend on it
+    "policy": Lib(["oc_policy.hip"], ["oc_policy.h"], ["oc_policy_device.h"], _PLAIN_FLAGS,
+                  os.path.join(CSRC, "liboc_policy.so")),
+    # the host-I/O library (include/oc_hostio.h): the numpy boundary's pack-for-PCIe kernel
+    "hostio": Lib(["oc_hostio.hip"], ["oc_hostio.h"], [], _PLAIN_FLAGS, os.path.join(CSRC, "liboc_hostio.so")),
+    # the rollout-buffer library (include/oc_rollout.h): one-launch recording and the GAE kernel, whose
+    # float32 chain must reproduce stable-baselines3's operation order bit for bit: no contraction
+    "rollout": Lib(["oc_rollout.hip"], ["oc_rollout.h"], [], _PLAIN_FLAGS + ["-ffp-contract=off", "-fno-fast-math"],
+                   os.path.join(CSRC, "liboc_rollout.so")),
+}
 
 
 def hipcc_path():
@@ -49,13 +51,13 @@ def hipcc_path():
     raise RuntimeError("hipcc not found (set HIPCC=)")
 
 
-def needs_build(lib=LIB, sources=SOURCES, headers=HEADERS, local_headers=LOCAL_HEADERS):
-    if not os.path.exists(lib):
+def needs_build(rec=LIBS["hip"]):
+    if not os.path.exists(rec.lib):
         return True
-    deps = [os.path.join(CSRC, s) for s in list(sources) + list(local_headers)]
+    deps = [os.path.join(CSRC, s) for s in list(rec.sources) + list(rec.local_headers)]
     inc = os.path.join(CSRC, "..", "..", "include")
-    deps += [os.path.join(inc, f) for f in headers]
-    return os.path.getmtime(lib) < max(os.path.getmtime(d) for d in deps)
+    deps += [os.path.join(inc, f) for f in rec.headers]
+    return os.path.getmtime(rec.lib) < max(os.path.getmtime(d) for d in deps)
 
 
 def _compile(lib, sources, flags, verbose):
@@ -75,36 +77,19 @@ def _compile(lib, sources, flags, verbose):
     return lib
 
 
+def build_lib(name, force=False, verbose=False, extra_flags=()):
+    """Compile shared object `name` of LIBS into csrc/.  Returns the library path."""
+    rec = LIBS[name]
+    if not force and not needs_build(rec):
+        return rec.lib
+    return _compile(rec.lib, rec.sources, list(rec.flags) + list(extra_flags), verbose)
+
+
 def build(force=False, verbose=False, extra_flags=()):
     """Compile the stepper into csrc/liboc_hip.so.  Returns the library path."""
-    if not force and not needs_build():
-        return LIB
-    return _compile(LIB, SOURCES, FLAGS + list(extra_flags), verbose)
-
-
-def build_policy(force=False, verbose=False):
-    """Compile the MLP policy kernel (include/oc_policy.h) into csrc/liboc_policy.so."""
-    if not force and not needs_build(POLICY_LIB, POLICY_SOURCES, POLICY_HEADERS, POLICY_LOCAL_HEADERS):
-        return POLICY_LIB
-    return _compile(POLICY_LIB, POLICY_SOURCES, POLICY_FLAGS, verbose)
-
-
-def build_hostio(force=False, verbose=False):
-    """Compile the numpy boundary's pack kernel (include/oc_hostio.h) into csrc/liboc_hostio.so."""
-    if not force and not needs_build(HOSTIO_LIB, HOSTIO_SOURCES, HOSTIO_HEADERS, ()):
-        return HOSTIO_LIB
-    return _compile(HOSTIO_LIB, HOSTIO_SOURCES, POLICY_FLAGS, verbose)
-
-
-def build_rollout(force=False, verbose=False):
-    """Compile the rollout buffer's kernels (include/oc_rollout.h) into csrc/liboc_rollout.so."""
-    if not force and not needs_build(ROLLOUT_LIB, ROLLOUT_SOURCES, ROLLOUT_HEADERS, ()):
-        return ROLLOUT_LIB
-    return _compile(ROLLOUT_LIB, ROLLOUT_SOURCES, ROLLOUT_FLAGS, verbose)
+    return build_lib("hip", force, verbose, extra_flags)
 
 
 if __name__ == "__main__":
-    print(build(force=True, verbose=True))
-    print(build_policy(force=True, verbose=True))
-    print(build_hostio(force=True, verbose=True))
-    print(build_rollout(force=True, verbose=True))
+    for name in LIBS:
+        print(build_lib(name, force=True, verbose=True))

@@ -1,0 +1,371 @@
+"""The players an ``OvercookedVecEnv`` seats (see ``vec_env`` for the overview): ``RandomPartner``,
+``MLPPolicy``, ``TorchPolicyPartner``, ``RecurrentPolicyPartner``, ``FusedMLPPartner``."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .batched import OBS_KEYS, OBS_TYPE, pcg32_seed_states
+
+
+def rows_and_timestep(obs):
+    """(feature-major rows [F][n], timestep [n]) of an observation: an ``ObsView``'s own storage,
+    or -- an observation dict without ``rows`` (any other env) -- concatenated the slow way."""
+    rows = getattr(obs, "rows", None)
+    if rows is None:
+        rows = torch.cat([obs[k].reshape(obs[k].shape[0], -1) for k in OBS_KEYS], dim=1).T
+    ts = getattr(obs, "timestep", None)
+    return rows, ts if ts is not None else obs["timestep"].reshape(-1)
+
+
+class _Seat:
+    """What the players built on ``act_into(obs, move_row, comm_row)`` share."""
+    sample = False
+
+    def _pick(self, logits, dim):
+        if self.sample:     # argmax(logits - log E), E ~ Exp(1)  ==  a categorical sample
+            logits = logits - torch.empty_like(logits).exponential_().log_()
+        return logits.argmax(dim=dim)
+
+    def __call__(self, obs):
+        n = next(iter(obs.values())).shape[0]
+        out = torch.empty((2, n), dtype=torch.int32, device=self.device)
+        self.act_into(obs, out[0], out[1])
+        return out.T
+
+
+class RandomPartner(_Seat):
+    """Uniform random partner (move 0..3, comm 0..C-1) from a PCG32 stream per env.  In the
+    partner seat of an ``OvercookedVecEnv`` it costs NO launch: the fused step kernel draws the
+    actions itself (``oc_step_opts.alt_rng``, include/oc_hip.h) and reports them in action rows
+    2, 3.  Anywhere else (``act_into`` / call) it is one launch of ``oc_random_actions``."""
+    graph_safe = True
+    in_kernel = True            # OvercookedVecEnv hands `rng_state(n)` to the step kernel
+
+    def __init__(self, num_comm, seed=0, device="cuda"):
+        self.C = int(num_comm)
+        self.seed = int(seed)
+        self.device = torch.device(device)
+        self._L = _lib.load()
+        self._rng = None
+
+    def rng_state(self, n):
+        """int32 [n] tensor holding the n PCG32 states (uint32 bit patterns)."""
+        return self._state(n)
+
+    def _state(self, n):
+        if self._rng is None or self._rng.numel() != n:
+            self._rng = pcg32_seed_states(self.seed, (n,), self.device)
+        return self._rng
+
+    def act_into(self, obs, move_row, comm_row):
+        n = move_row.numel()
+        _lib.call(self._L, "oc_random_actions", move_row.device.index, self._state(n).data_ptr(),
+                  move_row.data_ptr(), comm_row.data_ptr(), self.C, n)
+
+    def get_state(self, n):
+        """A copy of the generator state for n envs (allocated on first use)."""
+        return self._state(n).clone()
+
+    def set_state(self, st):
+        self._state(st.numel()).copy_(st)
+
+
+class MLPPolicy(torch.nn.Module):
+    """A small two-layer policy over get_observation2's 22 + S + 2C features (+ timestep):
+    returns (move logits [4][n], comm logits [C][n]).  Feature-major on purpose: the kernel
+    leaves a viewer's observation as [F][n] rows in HBM (float32 with ``obs_dtype=float32``), so
+    the first layer is one GEMM on those rows as they lie -- no gather, no transpose, no concat.
+    An observation dict without ``rows`` (any other env) is concatenated the slow way."""
+    feature_major = True
+
+    def __init__(self, num_subtasks, num_comm, hidden=64, seed=0):
+        super().__init__()
+        F = 22 + int(num_subtasks) + 2 * int(num_comm)
+        g = torch.Generator().manual_seed(int(seed))
+        init = lambda *shape: torch.nn.Parameter(
+            (torch.rand(shape, generator=g) * 2 - 1) / float(np.sqrt(shape[-1])))
+        self.w1, self.b1, self.wt = init(hidden, F), init(hidden, 1), init(hidden, 1)
+        self.w2, self.b2 = init(4 + int(num_comm), hidden), init(4 + int(num_comm), 1)
+        self.C = int(num_comm)
+
+    def forward(self, obs):
+        rows, ts = rows_and_timestep(obs)
+        ts = ts.unsqueeze(0)
+        if rows.dtype != torch.float32:
+            rows = rows.to(torch.float32)
+        h = torch.addmm(self.b1, self.w1, rows)                 # [H][n]
+        h = torch.addcmul(h, self.wt, ts.to(torch.float32))
+        out = torch.addmm(self.b2, self.w2, torch.tanh_(h))     # [4 + C][n]
+        return out[:4], out[4:]
+
+
+class TorchPolicyPartner(_Seat):
+    """A torch module in the partner (or ego) seat.  ``policy(obs) -> (move_logits,
+    comm_logits)``, each [n, k] -- or [k, n] when ``policy.feature_major`` is true.  Actions are
+    the argmax (``sample=False``) or a categorical sample (Gumbel-max on the default CUDA
+    generator, so the draw is hipGraph-capturable), written straight into the kernel's action
+    rows.  ``update(rewards, dones)`` -- pantheonrl's ``Agent.update`` -- is forwarded to
+    ``on_update`` (e.g. a rollout buffer's add), called after every step."""
+
+    def __init__(self, policy, sample=True, seed=None, device="cuda", on_update=None):
+        self.policy = policy
+        self.sample = bool(sample)
+        self.device = torch.device(device)
+        self.on_update = on_update
+        # stateless between steps and fixed-shape => one capture serves every later step
+        self.graph_safe = on_update is None
+        if seed is not None:
+            with torch.cuda.device(self.device):
+                torch.cuda.manual_seed(int(seed))
+
+    @torch.no_grad()
+    def act_into(self, obs, move_row, comm_row):
+        mv, cm = self.policy(obs)
+        dim = 0 if getattr(self.policy, "feature_major", False) else 1
+        move_row.copy_(self._pick(mv, dim))
+        comm_row.copy_(self._pick(cm, dim))
+
+    def update(self, rewards, dones):
+        if self.on_update is not None:
+            self.on_update(rewards, dones)
+
+
+class RecurrentPolicyPartner(_Seat):
+    """A STATEFUL torch policy in the partner (or ego) seat: the batched form of what the
+    reference seats there -- ``OnPolicyAgent(RecurrentPPO('MultiInputPolicy', ...))``
+    (trainer.py:92-112; pantheonrl/common/agents.py:112-214; sb3_contrib's recurrent policies
+    carry LSTM states per env and reset them where ``episode_starts`` is set).
+
+        policy(obs, state, episode_start) -> (move_logits, comm_logits, new_state[, value])
+
+    ``obs``: the viewer's ``ObsView`` ([n, k] keys, ``rows`` [F][n], ``timestep``); ``state``: a
+    tuple of ``[n, ...]`` tensors OWNED BY THE PARTNER (updated in place, so a captured graph keeps
+    their addresses); ``episode_start``: float32 [n], 1 where the env's previous step returned done
+    (the step kernel's ``done`` row, handed over by ``update``) and for every env on the first step
+    after a reset -- SB3's ``_last_episode_starts``.  With ``mask_state`` (default) the partner
+    itself puts the initial state back into the rows of starting envs before the call, so a policy
+    that ignores ``episode_start`` is still correct.  Logits are ``[n, k]``, or ``[k, n]`` when
+    ``policy.feature_major``; ``value`` is optional ([n] or [n, 1]).
+
+    Actions: argmax, or a categorical sample (Gumbel-max on the default CUDA generator:
+    hipGraph-capturable), written into the kernel's action rows; their log-probability under the
+    policy is computed either way.  ``sink`` (a ``RolloutSink``) records (obs, action, log_prob,
+    value, episode_start) at ``act_into`` and (reward, done) at ``update`` WITHOUT leaving the
+    device or the graph; ``on_update(rewards, dones)`` is the host-side learner hook (it switches
+    graph capture off, as for ``TorchPolicyPartner``)."""
+
+    def __init__(self, policy, state, sample=True, seed=None, device="cuda", sink=None, on_update=None,
+                 mask_state=True):
+        self.policy = policy
+        self.sample = bool(sample)
+        self.device = torch.device(device)
+        self.sink = sink
+        self.on_update = on_update
+        self.mask_state = bool(mask_state)
+        self.graph_safe = on_update is None
+        state = tuple(state) if isinstance(state, (tuple, list)) else (state,)
+        self.initial = tuple(s.detach().clone().to(self.device) for s in state)
+        self.state = tuple(s.clone() for s in self.initial)
+        n = self.state[0].shape[0]
+        self.episode_start = torch.ones(n, dtype=torch.float32, device=self.device)
+        self.log_prob = torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.value = torch.zeros(n, dtype=torch.float32, device=self.device)
+        if seed is not None:
+            with torch.cuda.device(self.device):
+                torch.cuda.manual_seed(int(seed))
+
+    def reset(self):
+        """A fresh rollout: every env starts an episode (called by ``reset_tensors``)."""
+        self.episode_start.fill_(1.0)
+        for s, s0 in zip(self.state, self.initial):
+            s.copy_(s0)
+
+    @torch.no_grad()
+    def act_into(self, obs, move_row, comm_row):
+        es = self.episode_start
+        if self.mask_state:
+            for s, s0 in zip(self.state, self.initial):
+                s.copy_(torch.where(es.view((-1,) + (1,) * (s.dim() - 1)) > 0, s0, s))
+        out = self.policy(obs, self.state, es)
+        mv, cm, new_state = out[0], out[1], out[2]
+        value = out[3] if len(out) > 3 else None
+        dim = 0 if getattr(self.policy, "feature_major", False) else 1
+        a_mv, a_cm = self._pick(mv, dim), self._pick(cm, dim)
+        lp = (torch.log_softmax(mv.float(), dim=dim).gather(dim, a_mv.unsqueeze(dim)).squeeze(dim)
+              + torch.log_softmax(cm.float(), dim=dim).gather(dim, a_cm.unsqueeze(dim)).squeeze(dim))
+        move_row.copy_(a_mv)
+        comm_row.copy_(a_cm)
+        self.log_prob.copy_(lp)
+        if value is not None:
+            self.value.copy_(value.reshape(-1))
+        new_state = tuple(new_state) if isinstance(new_state, (tuple, list)) else (new_state,)
+        for s, ns in zip(self.state, new_state):
+            s.copy_(ns)
+        if self.sink is not None:
+            rows, ts = rows_and_timestep(obs)
+            self.sink.add(rows, ts, move_row, comm_row, lp, value, es)
+
+    def update(self, rewards, dones):
+        """pantheonrl's ``Agent.update(reward, done)`` for the batch: ``dones`` become the next
+        step's ``episode_start`` (agents.py:207-208), the reward joins the recorded transition."""
+        self.episode_start.copy_(dones)
+        if self.sink is not None:
+            self.sink.add_reward(rewards, dones)
+        if self.on_update is not None:
+            self.on_update(rewards, dones)
+
+    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
+        """What ``OnPolicyAgent.get_action`` does on a full buffer before ``train()`` (agents.py:127-131):
+        ``buf.compute_returns_and_advantage(last_values=self.values, dones=self._last_episode_starts[0])``
+        with the values of the last ``act_into`` and the last ``done`` row.  Returns the sink's
+        (advantages, returns); the sink is NOT reset -- the caller does that after its update
+        (agents.py:158)."""
+        if self.sink is None:
+            raise ValueError("finish_rollout needs a sink")
+        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
+
+    def get_state(self, n=None):
+        return (tuple(s.clone() for s in self.state), self.episode_start.clone(), self.log_prob.clone(),
+                self.value.clone(), None if self.sink is None else self.sink.get_state())
+
+    def set_state(self, st):
+        for s, v in zip(self.state, st[0]):
+            s.copy_(v)
+        self.episode_start.copy_(st[1])
+        self.log_prob.copy_(st[2])
+        self.value.copy_(st[3])
+        if self.sink is not None:
+            self.sink.set_state(st[4])
+
+
+class FusedMLPPartner:
+    """An ``MLPPolicy`` in the partner (or ego) seat as ONE launch of the hand-written policy
+    kernel (include/oc_policy.h, csrc/oc_policy.hip): both products on the matrix cores
+    (v_mfma_f32_32x32x16_f16, one wave = 32 envs, the hidden layer never leaves the accumulator
+    registers), tanh, a categorical sample from two PCG32 streams per env, and the result written as
+    the int32 [n][2] (move, comm) pairs the step kernel consumes as they lie.  What
+    ``TorchPolicyPartner(MLPPolicy(...))`` does in ~12 torch launches.  Two of them (ego + partner)
+    share one launch (``FusedMLPPartner.launch``).  Weights are packed once (``refresh()`` after an
+    optimiser step); fp16 operands, fp32 accumulation: logits within 2e-2 of the fp32 module's."""
+    graph_safe = True
+    _seats = 0          # partners built so far: the default stream seed differs from seat to seat
+
+    def __init__(self, policy, sample=True, seed=None, device="cuda", keep_logits=False):
+        # seed=None: a different default per partner built (two seats left at their defaults -- an
+        # ego and a partner -- must not share per-env random streams: their samples would use the
+        # same uniform draw every step); pass a seed for a reproducible stream
+        if seed is None:
+            seed = 0x5EED + 1000003 * FusedMLPPartner._seats
+        FusedMLPPartner._seats += 1
+        if not isinstance(policy, MLPPolicy):
+            raise TypeError("FusedMLPPartner runs gym_comm_amd.vec_env.MLPPolicy; wrap any other module "
+                            "in TorchPolicyPartner")
+        if policy.w1.shape[0] != 64:
+            raise ValueError("the fused kernel has 64 hidden units (got %d)" % policy.w1.shape[0])
+        if not 1 <= policy.C <= 16:
+            raise ValueError("the fused kernel samples at most 16 comm channels (got %d)" % policy.C)
+        self.policy, self.sample, self.seed = policy, bool(sample), int(seed)
+        self.device = torch.device(device)
+        self.keep_logits = bool(keep_logits)
+        self._L = _lib.load(lib="policy")
+        self.F = int(policy.w1.shape[1])
+        self.C = int(policy.C)
+        self._w = None
+        self._rng = self.pairs = self.logits = None
+        self.refresh()
+
+    def refresh(self):
+        """(Re)pack the module's current weights into MFMA fragment order and upload them."""
+        L, pol = self._L, self.policy
+        f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+        fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        ks = L.oc_policy_ksteps(self.F)
+        w1, wt, b1, w2, b2 = (f32(t) for t in (pol.w1, pol.wt, pol.b1, pol.w2, pol.b2))
+        o1 = np.zeros((2, ks, 64, 8), np.uint16)
+        o2 = np.zeros((4, 64, 8), np.uint16)
+        ob = np.zeros((64, 16), np.float32)
+        for rc, what in ((L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), self.F,
+                                              o1.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w1"),
+                         (L.oc_policy_pack_w2(fp(w2), self.C, o2.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w2"),
+                         (L.oc_policy_pack_b2(fp(b2.reshape(-1)), fp(w2), self.C, fp(ob)), "oc_policy_pack_b2")):
+            _lib.check(rc, what, L)
+        dev = self.device
+        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(dev) for a in (o1, o2, ob))
+        if self._w is None:
+            self._w = new
+        else:                       # in place: a captured graph keeps the addresses
+            for old, cur in zip(self._w, new):
+                old.copy_(cur)
+
+    def _buffers(self, n):
+        if self.pairs is None or self.pairs.shape[0] != n:
+            self._rng = pcg32_seed_states(self.seed, (2, n), self.device)
+            self.pairs = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+            self.logits = (torch.zeros((4 + self.C, n), dtype=torch.float32, device=self.device)
+                           if self.keep_logits else None)
+
+    def _player(self, rows):
+        n = rows.shape[1]
+        if rows.shape[0] != self.F:
+            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
+        self._buffers(n)
+        return _lib.PolicyPlayer(rows.data_ptr(), self._w[0].data_ptr(), self._w[1].data_ptr(),
+                                 self._w[2].data_ptr(), self._rng.data_ptr() if self.sample else None,
+                                 self.pairs.data_ptr(), self.logits.data_ptr() if self.logits is not None else None)
+
+    @staticmethod
+    def launch(players, rows, timestep):
+        """One launch for one or two FusedMLPPartner, each on its own observation rows ([F][n]
+        views of the env's obs tensor); their ``pairs`` tensors hold the result."""
+        first = players[0]
+        if any(pl.F != first.F or pl.C != first.C for pl in players):
+            raise ValueError("players of one launch share F and C")
+        arr = (_lib.PolicyPlayer * len(players))(*[pl._player(r) for pl, r in zip(players, rows)])
+        _lib.call(first._L, "oc_policy_mlp", rows[0].device.index, arr, len(players), timestep.data_ptr(),
+                  first.F, first.C, OBS_TYPE[rows[0].dtype], rows[0].shape[1])
+
+    _PCG_MULT, _PCG_INC = 747796405, 2891336453          # csrc/oc_policy_device.h: pcg32
+    _PCG_MULT_INV = pow(747796405, -1, 1 << 32)
+
+    def rewind_rng(self):
+        """Step both PCG32 streams of every env back by ONE draw (the generator's state update is
+        an invertible affine map mod 2^32): the next evaluation repeats the last one's draw.  How a
+        one-launch closed loop re-primes after a reset without leaving the sequence the two-launch
+        form walks (``ClosedLoop.prime``)."""
+        if self._rng is None or not self.sample:
+            return
+        s = self._rng.to(torch.int64) & 0xFFFFFFFF
+        s = ((s - self._PCG_INC) * self._PCG_MULT_INV) & 0xFFFFFFFF
+        self._rng.copy_(torch.where(s >= (1 << 31), s - (1 << 32), s).to(torch.int32))
+
+    def step_policy(self, n):
+        """(w1, w2, b2, rng) device addresses for oc_step_opts.policy (the step kernel evaluates
+        this policy itself; its result lands in ``self.pairs``)."""
+        self._buffers(n)
+        return (self._w[0].data_ptr(), self._w[1].data_ptr(), self._w[2].data_ptr(),
+                self._rng.data_ptr() if self.sample else None)
+
+    def pairs_for(self, obs):
+        """obs: an ``ObsView`` of the env (``rows`` [F][n], ``timestep``).  Returns int32 [n][2]."""
+        FusedMLPPartner.launch([self], [obs.rows], obs.timestep)
+        return self.pairs
+
+    def act_into(self, obs, move_row, comm_row):       # the generic partner protocol (two more copies)
+        pr = self.pairs_for(obs)
+        move_row.copy_(pr[:, 0])
+        comm_row.copy_(pr[:, 1])
+
+    def __call__(self, obs):
+        return self.pairs_for(obs)
+
+    def get_state(self, n):
+        """The player's mutable state: its random streams and its pairs (in a one-launch closed
+        loop the pairs are the NEXT step's actions, i.e. state)."""
+        self._buffers(n)
+        return self._rng.clone(), self.pairs.clone()
+
+    def set_state(self, st):
+        self._rng.copy_(st[0])
+        self.pairs.copy_(st[1])

@@ -42,8 +42,6 @@ structural stand-in with the same methods.  ``step_tensors`` is the zero-copy va
 policies that live on the GPU; the numpy API packs a step's arrays with one launch of
 ``oc_pack_host`` (include/oc_hostio.h) and one PCIe copy.
 """
-import contextlib
-import ctypes
 import os
 import weakref
 
@@ -51,8 +49,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batched import BatchedOvercooked, OBS_KEYS
+from .batched import BatchedOvercooked, OBS_TYPE
 from .envs import OvercookedEnvironment, _arg, make_spaces
+from .partners import (FusedMLPPartner, MLPPolicy, RandomPartner,  # noqa: F401 (re-exported)
+                       RecurrentPolicyPartner, TorchPolicyPartner)
+from .rollout import RolloutSink  # noqa: F401 (re-exported)
 
 try:                                                    # pragma: no cover - SB3 absent in CI image
     from stable_baselines3.common.vec_env import VecEnv as _VecEnvBase
@@ -85,563 +86,6 @@ class ObsView(dict):
     (f64 [n]).  The same objects every step; the next step overwrites their contents."""
     rows = None
     timestep = None
-
-
-class RandomPartner:
-    """Uniform random partner (move 0..3, comm 0..C-1) from a PCG32 stream per env.  In the
-    partner seat of an ``OvercookedVecEnv`` it costs NO launch: the fused step kernel draws the
-    actions itself (``oc_step_opts.alt_rng``, include/oc_hip.h) and reports them in action rows
-    2, 3.  Anywhere else (``act_into`` / call) it is one launch of ``oc_random_actions``."""
-    graph_safe = True
-    in_kernel = True            # OvercookedVecEnv hands `rng_state(n)` to the step kernel
-
-    def __init__(self, num_comm, seed=0, device="cuda"):
-        self.C = int(num_comm)
-        self.seed = int(seed)
-        self.device = torch.device(device)
-        self._L = _lib.load()
-        self._rng = None
-
-    def rng_state(self, n):
-        """int32 [n] tensor holding the n PCG32 states (uint32 bit patterns)."""
-        return self._state(n)
-
-    def _state(self, n):
-        if self._rng is None or self._rng.numel() != n:
-            g = torch.Generator(device="cpu").manual_seed(self.seed)
-            self._rng = torch.randint(0, 2 ** 31 - 1, (n,), generator=g, dtype=torch.int64
-                                      ).to(torch.int32).to(self.device)
-        return self._rng
-
-    def act_into(self, obs, move_row, comm_row):
-        n = move_row.numel()
-        dev = move_row.device.index
-        if torch.cuda.current_device() != dev:
-            with torch.cuda.device(dev):
-                return self.act_into(obs, move_row, comm_row)
-        rc = self._L.oc_random_actions(self._state(n).data_ptr(), move_row.data_ptr(), comm_row.data_ptr(),
-                                       self.C, n, torch._C._cuda_getCurrentRawStream(dev))
-        if rc:
-            _lib.check(rc, "oc_random_actions", self._L)
-
-    def get_state(self, n):
-        """A copy of the generator state for n envs (allocated on first use)."""
-        return self._state(n).clone()
-
-    def set_state(self, st):
-        self._state(st.numel()).copy_(st)
-
-    def __call__(self, obs):
-        n = next(iter(obs.values())).shape[0]
-        out = torch.empty((2, n), dtype=torch.int32, device=self.device)
-        self.act_into(obs, out[0], out[1])
-        return out.T
-
-
-class MLPPolicy(torch.nn.Module):
-    """A small two-layer policy over get_observation2's 22 + S + 2C features (+ timestep):
-    returns (move logits [4][n], comm logits [C][n]).  Feature-major on purpose: the kernel
-    leaves a viewer's observation as [F][n] rows in HBM (float32 with ``obs_dtype=float32``), so
-    the first layer is one GEMM on those rows as they lie -- no gather, no transpose, no concat.
-    An observation dict without ``rows`` (any other env) is concatenated the slow way."""
-    feature_major = True
-
-    def __init__(self, num_subtasks, num_comm, hidden=64, seed=0):
-        super().__init__()
-        F = 22 + int(num_subtasks) + 2 * int(num_comm)
-        g = torch.Generator().manual_seed(int(seed))
-        init = lambda *shape: torch.nn.Parameter(
-            (torch.rand(shape, generator=g) * 2 - 1) / float(np.sqrt(shape[-1])))
-        self.w1, self.b1, self.wt = init(hidden, F), init(hidden, 1), init(hidden, 1)
-        self.w2, self.b2 = init(4 + int(num_comm), hidden), init(4 + int(num_comm), 1)
-        self.C = int(num_comm)
-
-    def forward(self, obs):
-        rows = getattr(obs, "rows", None)
-        if rows is None:
-            rows = torch.cat([obs[k].reshape(obs[k].shape[0], -1) for k in OBS_KEYS], dim=1).T
-            ts = obs["timestep"].reshape(1, -1)
-        else:
-            ts = obs.timestep.unsqueeze(0)
-        if rows.dtype != torch.float32:
-            rows = rows.to(torch.float32)
-        h = torch.addmm(self.b1, self.w1, rows)                 # [H][n]
-        h = torch.addcmul(h, self.wt, ts.to(torch.float32))
-        out = torch.addmm(self.b2, self.w2, torch.tanh_(h))     # [4 + C][n]
-        return out[:4], out[4:]
-
-
-class TorchPolicyPartner:
-    """A torch module in the partner (or ego) seat.  ``policy(obs) -> (move_logits,
-    comm_logits)``, each [n, k] -- or [k, n] when ``policy.feature_major`` is true.  Actions are
-    the argmax (``sample=False``) or a categorical sample (Gumbel-max on the default CUDA
-    generator, so the draw is hipGraph-capturable), written straight into the kernel's action
-    rows.  ``update(rewards, dones)`` -- pantheonrl's ``Agent.update`` -- is forwarded to
-    ``on_update`` (e.g. a rollout buffer's add), called after every step."""
-
-    def __init__(self, policy, sample=True, seed=None, device="cuda", on_update=None):
-        self.policy = policy
-        self.sample = bool(sample)
-        self.device = torch.device(device)
-        self.on_update = on_update
-        # stateless between steps and fixed-shape => one capture serves every later step
-        self.graph_safe = on_update is None
-        if seed is not None:
-            with torch.cuda.device(self.device):
-                torch.cuda.manual_seed(int(seed))
-
-    def _pick(self, logits, dim):
-        if self.sample:     # argmax(logits - log E), E ~ Exp(1)  ==  a categorical sample
-            logits = logits - torch.empty_like(logits).exponential_().log_()
-        return logits.argmax(dim=dim)
-
-    @torch.no_grad()
-    def act_into(self, obs, move_row, comm_row):
-        mv, cm = self.policy(obs)
-        dim = 0 if getattr(self.policy, "feature_major", False) else 1
-        move_row.copy_(self._pick(mv, dim))
-        comm_row.copy_(self._pick(cm, dim))
-
-    def __call__(self, obs):
-        n = next(iter(obs.values())).shape[0]
-        out = torch.empty((2, n), dtype=torch.int32, device=self.device)
-        self.act_into(obs, out[0], out[1])
-        return out.T
-
-    def update(self, rewards, dones):
-        if self.on_update is not None:
-            self.on_update(rewards, dones)
-
-
-class RolloutSink:
-    """What pantheonrl's ``OnPolicyAgent`` keeps per step in its rollout buffer -- ``buf.add(obs,
-    action, [0], episode_start, value, log_prob)`` in ``get_action`` and ``buf.rewards[pos - 1] +=
-    reward`` in ``update`` (pantheonrl/common/agents.py:112-214) -- for a whole batch, in
-    PREALLOCATED ``[n_steps][...][n]`` device tensors whose write position is itself a device scalar.
-    Every write is an ``index_copy_`` / ``index_add_`` on that scalar, so recording neither
-    synchronises nor changes shape: it can sit inside a captured hipGraph (a learner's hook that runs
-    host code per step cannot).  ``full()`` / ``steps()`` read the counter (one sync, when asked);
-    ``reset()`` starts the next rollout.  Past ``n_steps`` the position wraps (a ring).
-
-    ``fused=True``: the same tensors and counters, written by ``liboc_rollout.so``
-    (include/oc_rollout.h) -- ONE launch per ``add``, one per ``add_reward`` (about a dozen and four
-    torch launches otherwise), storing the same bits -- plus ``advantages`` / ``returns`` filled by
-    ONE launch of ``compute_returns_and_advantage`` (the third buffer call of agents.py:127-131)."""
-
-    _OBS_TYPE = {torch.int32: 0, torch.int8: 1, torch.float32: 2}      # include/oc_hostio.h: obs_type
-
-    def __init__(self, n_steps, n, rows, device="cuda", obs_dtype=torch.int32, fused=False):
-        dev = torch.device(device)
-        T = self.n_steps = int(n_steps)
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.obs = z((T, int(rows), n), obs_dtype)       # the viewer's [F][n] rows as they lie
-        self.timestep = z((T, n), torch.float64)
-        self.actions = z((T, 2, n), torch.int32)         # (move, comm)
-        self.log_probs = z((T, n), torch.float32)
-        self.values = z((T, n), torch.float32)
-        self.rewards = z((T, n), torch.float64)
-        self.episode_starts = z((T, n), torch.float32)
-        self.dones = z((T, n), torch.int32)
-        self.pos = z((1,), torch.int64)                  # next slot
-        self.last = z((1,), torch.int64)                 # slot of the most recent add()
-        self.count = z((1,), torch.int64)                # adds since reset()
-        self.advantages = self.returns = self.ticket = None
-        self.fused = bool(fused)
-        if self.fused:
-            # one launch per add / add_reward / compute_returns_and_advantage (include/oc_rollout.h)
-            if dev.type != "cuda":
-                raise ValueError("the fused sink's kernels run on the GPU (device=%r); there is no CPU fallback" % (device,))
-            if obs_dtype not in self._OBS_TYPE:
-                raise ValueError("the fused sink stores int32, int8 or float32 rows (got %s)" % (obs_dtype,))
-            self._L = _lib.load_rollout()
-            self.ticket = z((1,), torch.int32)           # the add kernel's workgroup ticket: 0 between calls
-            self.advantages = z((T, n), torch.float32)
-            self.returns = z((T, n), torch.float32)
-            self._dev = dev.index if dev.index is not None else torch.cuda.current_device()
-            self._buf = _lib.RolloutBuf(
-                *[t.data_ptr() for t in (self.obs, self.timestep, self.actions, self.log_probs, self.values,
-                                         self.episode_starts, self.rewards, self.dones, self.pos, self.last,
-                                         self.count, self.ticket, self.advantages, self.returns)],
-                n, T, int(rows), self._OBS_TYPE[obs_dtype])
-
-    def _call(self, name, *args):
-        """One entry point of liboc_rollout.so on the current torch stream of the sink's device."""
-        dev = self._dev
-        with (contextlib.nullcontext() if torch.cuda.current_device() == dev else torch.cuda.device(dev)):
-            rc = getattr(self._L, name)(ctypes.byref(self._buf), *args, torch._C._cuda_getCurrentRawStream(dev))
-        if rc:
-            raise _lib.OcError("%s failed (%d): %s" % (name, rc, self._L.oc_rollout_last_error().decode()))
-
-    @staticmethod
-    def _row(t, dtype, n):
-        """t as the kernel reads it: `dtype`, contiguous, n elements (torch converts what is not)."""
-        if t.dtype != dtype:
-            t = t.to(dtype)
-        t = t.reshape(-1)
-        if t.numel() != n:
-            raise ValueError("a row of %d elements where the sink holds %d envs" % (t.numel(), n))
-        return t if t.is_contiguous() else t.contiguous()
-
-    def add(self, rows, timestep, move, comm, log_prob, value, episode_start):
-        if self.fused:
-            n = self.obs.shape[2]
-            if rows.dtype != self.obs.dtype or rows.shape != self.obs.shape[1:]:
-                raise ValueError("rows %s %s where the sink holds %s %s" % (
-                    rows.dtype, tuple(rows.shape), self.obs.dtype, tuple(self.obs.shape[1:])))
-            # converted exactly as the torch path below converts them; what already lies as the kernel
-            # reads it (the env's rows, its action rows, the partner's float32 rows) is passed as it is
-            rows = rows if rows.is_contiguous() else rows.contiguous()
-            keep = (rows, self._row(timestep, torch.float64, n), self._row(move, torch.int32, n),
-                    self._row(comm, torch.int32, n), self._row(log_prob, torch.float32, n),
-                    None if value is None else self._row(value, torch.float32, n),
-                    self._row(episode_start, torch.float32, n))
-            self._call("oc_rollout_add", *[None if t is None else t.data_ptr() for t in keep])
-            return
-        i = self.pos
-        self.obs.index_copy_(0, i, rows.unsqueeze(0))
-        self.timestep.index_copy_(0, i, timestep.unsqueeze(0))
-        self.actions.index_copy_(0, i, torch.stack([move, comm]).to(torch.int32).unsqueeze(0))
-        self.log_probs.index_copy_(0, i, log_prob.to(torch.float32).unsqueeze(0))
-        if value is not None:
-            self.values.index_copy_(0, i, value.reshape(1, -1).to(torch.float32))
-        self.episode_starts.index_copy_(0, i, episode_start.to(torch.float32).unsqueeze(0))
-        self.rewards.index_fill_(0, i, 0.0)              # buf.add(..., [0], ...): update() adds
-        self.last.copy_(i)
-        self.pos.add_(1).remainder_(self.n_steps)
-        self.count.add_(1)
-
-    def add_reward(self, rewards, dones):
-        """``update(reward, done)`` of the step the most recent ``add`` belongs to."""
-        if self.fused:
-            n = self.obs.shape[2]
-            keep = (self._row(rewards, torch.float64, n), self._row(dones, torch.int32, n))
-            self._call("oc_rollout_add_reward", keep[0].data_ptr(), keep[1].data_ptr())
-            return
-        self.rewards.index_add_(0, self.last, rewards.to(torch.float64).unsqueeze(0))
-        self.dones.index_copy_(0, self.last, dones.to(torch.int32).unsqueeze(0))
-
-    def compute_returns_and_advantage(self, last_values, dones, gamma=0.99, gae_lambda=0.95):
-        """stable-baselines3's ``RolloutBuffer.compute_returns_and_advantage`` over the recorded steps
-        (what ``OnPolicyAgent.get_action`` calls on a full buffer before ``train()``, agents.py:127-131):
-        ``last_values`` are the values of the observation after the newest step, ``dones`` whether
-        that step ended its episode.  With L = min(count, n_steps), step k of L lives in slot
-        (pos - L + k) mod n_steps; per env, in float32 and in this order (include/oc_rollout.h):
-
-            delta = ((float)rewards[k] + (g * next_value) * next_non_terminal) - values[k]
-            last  = delta + ((g_lambda * next_non_terminal) * last)
-            advantages[k] = last;  returns[k] = last + values[k]
-
-        Fills and returns ``(advantages, returns)``, float32 [n_steps][n]; slots that hold no step are
-        left as they were.  ``fused=True``: ONE launch, no synchronisation.  Otherwise the loop in
-        torch: a few launches per step and one read of the counters -- slow, and the same bits."""
-        n = self.obs.shape[2]
-        if self.fused:
-            keep = (self._row(last_values, torch.float32, n), self._row(dones, torch.float32, n))
-            self._call("oc_rollout_gae", keep[0].data_ptr(), keep[1].data_ptr(),
-                       ctypes.c_double(float(gamma)), ctypes.c_double(float(gae_lambda)))
-            return self.advantages, self.returns
-        if self.advantages is None:
-            self.advantages = torch.zeros_like(self.values)
-            self.returns = torch.zeros_like(self.values)
-        T = self.n_steps
-        g = float(np.float32(gamma))                                # exact in float32 from here on
-        gl = float(np.float32(float(gamma) * float(gae_lambda)))    # the product in double, as SB3 forms it
-        L, pos = min(self.steps(), T), int(self.pos.item())
-        nv = last_values.reshape(-1).to(torch.float32)
-        nnt = 1.0 - dones.reshape(-1).to(torch.float32)
-        last = torch.zeros_like(nv)
-        for k in range(L - 1, -1, -1):
-            s = (pos - L + k) % T
-            v = self.values[s]
-            delta = (self.rewards[s].to(torch.float32) + (nv * g) * nnt) - v
-            last = delta + ((nnt * gl) * last)
-            self.advantages[s] = last
-            self.returns[s] = last + v
-            nv, nnt = v, 1.0 - self.episode_starts[s]
-        return self.advantages, self.returns
-
-    def steps(self):
-        return int(self.count.item())
-
-    def full(self):
-        return self.steps() >= self.n_steps
-
-    def reset(self):
-        self.pos.zero_()
-        self.last.zero_()
-        self.count.zero_()
-        if self.ticket is not None:
-            self.ticket.zero_()
-
-    def get_state(self):
-        return self.pos.clone(), self.last.clone(), self.count.clone()
-
-    def set_state(self, st):
-        self.pos.copy_(st[0])
-        self.last.copy_(st[1])
-        self.count.copy_(st[2])
-
-
-class RecurrentPolicyPartner:
-    """A STATEFUL torch policy in the partner (or ego) seat: the batched form of what the
-    reference seats there -- ``OnPolicyAgent(RecurrentPPO('MultiInputPolicy', ...))``
-    (trainer.py:92-112; pantheonrl/common/agents.py:112-214; sb3_contrib's recurrent policies
-    carry LSTM states per env and reset them where ``episode_starts`` is set).
-
-        policy(obs, state, episode_start) -> (move_logits, comm_logits, new_state[, value])
-
-    ``obs``: the viewer's ``ObsView`` ([n, k] keys, ``rows`` [F][n], ``timestep``); ``state``: a
-    tuple of ``[n, ...]`` tensors OWNED BY THE PARTNER (updated in place, so a captured graph keeps
-    their addresses); ``episode_start``: float32 [n], 1 where the env's previous step returned done
-    (the step kernel's ``done`` row, handed over by ``update``) and for every env on the first step
-    after a reset -- SB3's ``_last_episode_starts``.  With ``mask_state`` (default) the partner
-    itself puts the initial state back into the rows of starting envs before the call, so a policy
-    that ignores ``episode_start`` is still correct.  Logits are ``[n, k]``, or ``[k, n]`` when
-    ``policy.feature_major``; ``value`` is optional ([n] or [n, 1]).
-
-    Actions: argmax, or a categorical sample (Gumbel-max on the default CUDA generator:
-    hipGraph-capturable), written into the kernel's action rows; their log-probability under the
-    policy is computed either way.  ``sink`` (a ``RolloutSink``) records (obs, action, log_prob,
-    value, episode_start) at ``act_into`` and (reward, done) at ``update`` WITHOUT leaving the
-    device or the graph; ``on_update(rewards, dones)`` is the host-side learner hook (it switches
-    graph capture off, as for ``TorchPolicyPartner``)."""
-
-    def __init__(self, policy, state, sample=True, seed=None, device="cuda", sink=None, on_update=None,
-                 mask_state=True):
-        self.policy = policy
-        self.sample = bool(sample)
-        self.device = torch.device(device)
-        self.sink = sink
-        self.on_update = on_update
-        self.mask_state = bool(mask_state)
-        self.graph_safe = on_update is None
-        state = tuple(state) if isinstance(state, (tuple, list)) else (state,)
-        self.initial = tuple(s.detach().clone().to(self.device) for s in state)
-        self.state = tuple(s.clone() for s in self.initial)
-        n = self.state[0].shape[0]
-        self.episode_start = torch.ones(n, dtype=torch.float32, device=self.device)
-        self.log_prob = torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.value = torch.zeros(n, dtype=torch.float32, device=self.device)
-        if seed is not None:
-            with torch.cuda.device(self.device):
-                torch.cuda.manual_seed(int(seed))
-
-    def reset(self):
-        """A fresh rollout: every env starts an episode (called by ``reset_tensors``)."""
-        self.episode_start.fill_(1.0)
-        for s, s0 in zip(self.state, self.initial):
-            s.copy_(s0)
-
-    def _pick(self, logits, dim):
-        if self.sample:
-            logits = logits - torch.empty_like(logits).exponential_().log_()
-        return logits.argmax(dim=dim)
-
-    @torch.no_grad()
-    def act_into(self, obs, move_row, comm_row):
-        es = self.episode_start
-        if self.mask_state:
-            for s, s0 in zip(self.state, self.initial):
-                s.copy_(torch.where(es.view((-1,) + (1,) * (s.dim() - 1)) > 0, s0, s))
-        out = self.policy(obs, self.state, es)
-        mv, cm, new_state = out[0], out[1], out[2]
-        value = out[3] if len(out) > 3 else None
-        dim = 0 if getattr(self.policy, "feature_major", False) else 1
-        a_mv, a_cm = self._pick(mv, dim), self._pick(cm, dim)
-        lp = (torch.log_softmax(mv.float(), dim=dim).gather(dim, a_mv.unsqueeze(dim)).squeeze(dim)
-              + torch.log_softmax(cm.float(), dim=dim).gather(dim, a_cm.unsqueeze(dim)).squeeze(dim))
-        move_row.copy_(a_mv)
-        comm_row.copy_(a_cm)
-        self.log_prob.copy_(lp)
-        if value is not None:
-            self.value.copy_(value.reshape(-1))
-        new_state = tuple(new_state) if isinstance(new_state, (tuple, list)) else (new_state,)
-        for s, ns in zip(self.state, new_state):
-            s.copy_(ns)
-        if self.sink is not None:
-            rows = getattr(obs, "rows", None)
-            if rows is None:
-                rows = torch.cat([obs[k].reshape(obs[k].shape[0], -1) for k in OBS_KEYS], dim=1).T
-            ts = obs.timestep if getattr(obs, "timestep", None) is not None else obs["timestep"].reshape(-1)
-            self.sink.add(rows, ts, move_row, comm_row, lp, value, es)
-
-    def __call__(self, obs):
-        n = self.episode_start.numel()
-        out = torch.empty((2, n), dtype=torch.int32, device=self.device)
-        self.act_into(obs, out[0], out[1])
-        return out.T
-
-    def update(self, rewards, dones):
-        """pantheonrl's ``Agent.update(reward, done)`` for the batch: ``dones`` become the next
-        step's ``episode_start`` (agents.py:207-208), the reward joins the recorded transition."""
-        self.episode_start.copy_(dones)
-        if self.sink is not None:
-            self.sink.add_reward(rewards, dones)
-        if self.on_update is not None:
-            self.on_update(rewards, dones)
-
-    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
-        """What ``OnPolicyAgent.get_action`` does on a full buffer before ``train()`` (agents.py:127-131):
-        ``buf.compute_returns_and_advantage(last_values=self.values, dones=self._last_episode_starts[0])``
-        with the values of the last ``act_into`` and the last ``done`` row.  Returns the sink's
-        (advantages, returns); the sink is NOT reset -- the caller does that after its update
-        (agents.py:158)."""
-        if self.sink is None:
-            raise ValueError("finish_rollout needs a sink")
-        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
-
-    def get_state(self, n=None):
-        return (tuple(s.clone() for s in self.state), self.episode_start.clone(), self.log_prob.clone(),
-                self.value.clone(), None if self.sink is None else self.sink.get_state())
-
-    def set_state(self, st):
-        for s, v in zip(self.state, st[0]):
-            s.copy_(v)
-        self.episode_start.copy_(st[1])
-        self.log_prob.copy_(st[2])
-        self.value.copy_(st[3])
-        if self.sink is not None:
-            self.sink.set_state(st[4])
-
-
-class FusedMLPPartner:
-    """An ``MLPPolicy`` in the partner (or ego) seat as ONE launch of the hand-written policy
-    kernel (include/oc_policy.h, csrc/oc_policy.hip): both products on the matrix cores
-    (v_mfma_f32_32x32x16_f16, one wave = 32 envs, the hidden layer never leaves the accumulator
-    registers), tanh, a categorical sample from two PCG32 streams per env, and the result written as
-    the int32 [n][2] (move, comm) pairs the step kernel consumes as they lie.  What
-    ``TorchPolicyPartner(MLPPolicy(...))`` does in ~12 torch launches.  Two of them (ego + partner)
-    share one launch (``FusedMLPPartner.launch``).  Weights are packed once (``refresh()`` after an
-    optimiser step); fp16 operands, fp32 accumulation: logits within 2e-2 of the fp32 module's."""
-    graph_safe = True
-    _seats = 0          # partners built so far: the default stream seed differs from seat to seat
-
-    def __init__(self, policy, sample=True, seed=None, device="cuda", keep_logits=False):
-        # seed=None: a different default per partner built (two seats left at their defaults -- an
-        # ego and a partner -- must not share per-env random streams: their samples would use the
-        # same uniform draw every step, ADVICE r2); pass a seed for a reproducible stream
-        if seed is None:
-            seed = 0x5EED + 1000003 * FusedMLPPartner._seats
-        FusedMLPPartner._seats += 1
-        if not isinstance(policy, MLPPolicy):
-            raise TypeError("FusedMLPPartner runs gym_comm_amd.vec_env.MLPPolicy; wrap any other module "
-                            "in TorchPolicyPartner")
-        if policy.w1.shape[0] != 64:
-            raise ValueError("the fused kernel has 64 hidden units (got %d)" % policy.w1.shape[0])
-        if not 1 <= policy.C <= 16:
-            raise ValueError("the fused kernel samples at most 16 comm channels (got %d)" % policy.C)
-        self.policy, self.sample, self.seed = policy, bool(sample), int(seed)
-        self.device = torch.device(device)
-        self.keep_logits = bool(keep_logits)
-        self._L = _lib.load_policy()
-        self.F = int(policy.w1.shape[1])
-        self.C = int(policy.C)
-        self._w = None
-        self._rng = self.pairs = self.logits = None
-        self.refresh()
-
-    def refresh(self):
-        """(Re)pack the module's current weights into MFMA fragment order and upload them."""
-        L, pol = self._L, self.policy
-        f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
-        fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        ks = L.oc_policy_ksteps(self.F)
-        w1, wt, b1, w2, b2 = (f32(t) for t in (pol.w1, pol.wt, pol.b1, pol.w2, pol.b2))
-        o1 = np.zeros((2, ks, 64, 8), np.uint16)
-        o2 = np.zeros((4, 64, 8), np.uint16)
-        ob = np.zeros((64, 16), np.float32)
-        for rc, what in ((L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), self.F,
-                                              o1.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w1"),
-                         (L.oc_policy_pack_w2(fp(w2), self.C, o2.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w2"),
-                         (L.oc_policy_pack_b2(fp(b2.reshape(-1)), fp(w2), self.C, fp(ob)), "oc_policy_pack_b2")):
-            if rc:
-                raise _lib.OcError("%s failed: %s" % (what, L.oc_policy_last_error().decode()))
-        dev = self.device
-        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(dev) for a in (o1, o2, ob))
-        if self._w is None:
-            self._w = new
-        else:                       # in place: a captured graph keeps the addresses
-            for old, cur in zip(self._w, new):
-                old.copy_(cur)
-
-    def _buffers(self, n):
-        if self.pairs is None or self.pairs.shape[0] != n:
-            g = torch.Generator(device="cpu").manual_seed(self.seed)
-            self._rng = torch.randint(0, 2 ** 31 - 1, (2, n), generator=g, dtype=torch.int64
-                                      ).to(torch.int32).to(self.device)
-            self.pairs = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-            self.logits = (torch.zeros((4 + self.C, n), dtype=torch.float32, device=self.device)
-                           if self.keep_logits else None)
-
-    def _player(self, rows):
-        n = rows.shape[1]
-        if rows.shape[0] != self.F:
-            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
-        self._buffers(n)
-        return _lib.PolicyPlayer(rows.data_ptr(), self._w[0].data_ptr(), self._w[1].data_ptr(),
-                                 self._w[2].data_ptr(), self._rng.data_ptr() if self.sample else None,
-                                 self.pairs.data_ptr(), self.logits.data_ptr() if self.logits is not None else None)
-
-    @staticmethod
-    def launch(players, rows, timestep):
-        """One launch for one or two FusedMLPPartner, each on its own observation rows ([F][n]
-        views of the env's obs tensor); their ``pairs`` tensors hold the result."""
-        first = players[0]
-        if any(pl.F != first.F or pl.C != first.C for pl in players):
-            raise ValueError("players of one launch share F and C")
-        arr = (_lib.PolicyPlayer * len(players))(*[pl._player(r) for pl, r in zip(players, rows)])
-        ot = {torch.int32: 0, torch.int8: 1, torch.float32: 2}[rows[0].dtype]
-        dev = rows[0].device.index
-        n = rows[0].shape[1]
-        with (contextlib.nullcontext() if torch.cuda.current_device() == dev else torch.cuda.device(dev)):
-            rc = first._L.oc_policy_mlp(arr, len(players), timestep.data_ptr(), first.F, first.C, ot, n,
-                                        torch._C._cuda_getCurrentRawStream(dev))
-        if rc:
-            raise _lib.OcError("oc_policy_mlp failed (%d): %s" % (rc, first._L.oc_policy_last_error().decode()))
-
-    _PCG_MULT, _PCG_INC = 747796405, 2891336453          # csrc/oc_policy_device.h: pcg32
-    _PCG_MULT_INV = pow(747796405, -1, 1 << 32)
-
-    def rewind_rng(self):
-        """Step both PCG32 streams of every env back by ONE draw (the generator's state update is
-        an invertible affine map mod 2^32): the next evaluation repeats the last one's draw.  How a
-        one-launch closed loop re-primes after a reset without leaving the sequence the two-launch
-        form walks (``ClosedLoop.prime``)."""
-        if self._rng is None or not self.sample:
-            return
-        s = self._rng.to(torch.int64) & 0xFFFFFFFF
-        s = ((s - self._PCG_INC) * self._PCG_MULT_INV) & 0xFFFFFFFF
-        self._rng.copy_(torch.where(s >= (1 << 31), s - (1 << 32), s).to(torch.int32))
-
-    def step_policy(self, n):
-        """(w1, w2, b2, rng) device addresses for oc_step_opts.policy (the step kernel evaluates
-        this policy itself; its result lands in ``self.pairs``)."""
-        self._buffers(n)
-        return (self._w[0].data_ptr(), self._w[1].data_ptr(), self._w[2].data_ptr(),
-                self._rng.data_ptr() if self.sample else None)
-
-    def pairs_for(self, obs):
-        """obs: an ``ObsView`` of the env (``rows`` [F][n], ``timestep``).  Returns int32 [n][2]."""
-        FusedMLPPartner.launch([self], [obs.rows], obs.timestep)
-        return self.pairs
-
-    def act_into(self, obs, move_row, comm_row):       # the generic partner protocol (two more copies)
-        pr = self.pairs_for(obs)
-        move_row.copy_(pr[:, 0])
-        comm_row.copy_(pr[:, 1])
-
-    def __call__(self, obs):
-        return self.pairs_for(obs)
-
-    def get_state(self, n):
-        """The player's mutable state: its random streams and its pairs (in a one-launch closed
-        loop the pairs are the NEXT step's actions, i.e. state)."""
-        self._buffers(n)
-        return self._rng.clone(), self.pairs.clone()
-
-    def set_state(self, st):
-        self._rng.copy_(st[0])
-        self.pairs.copy_(st[1])
 
 
 class ClosedLoop:
@@ -918,6 +362,13 @@ class OvercookedVecEnv(_VecEnvBase):
                 self._act[2:4].copy_(pa.T)
         b.multi_step(self._act, auto_reset=auto_reset, ego_pairs=ego_pairs, alt_pairs=alt_pairs)
 
+    def _staged_pairs(self):
+        """int32 [n][2] on the device: where ego actions that the kernel cannot take as they lie are
+        staged (allocated on first use; the captured step's fixed input)."""
+        if self._ego_pairs is None:
+            self._ego_pairs = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self._b.device)
+        return self._ego_pairs
+
     def step_tensors(self, ego_actions=None):
         """ego_actions: int tensor [n, 2] on the device (None: already written into
         ``ego_action_rows``).  A contiguous int32 or int64 tensor is handed to the kernel as it
@@ -950,16 +401,12 @@ class OvercookedVecEnv(_VecEnvBase):
             if ea.dtype == torch.int32 and ea.is_contiguous() and not self._use_graph:
                 ego_pairs = ea                 # (the slow path keeps to int32: alt_pairs may join it)
             else:                       # other dtypes / layouts, or the captured graph's fixed input
-                if self._ego_pairs is None:
-                    self._ego_pairs = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=b.device)
-                self._ego_pairs.copy_(ea)
-                ego_pairs = self._ego_pairs
+                ego_pairs = self._staged_pairs()
+                ego_pairs.copy_(ea)
         term = None
         if self._use_graph:
-            if self._ego_pairs is None:
-                self._ego_pairs = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=b.device)
             if ego_pairs is None:       # ego rows written by the caller: bring them into the graph's input
-                self._ego_pairs.copy_(self._act[0:2].T)
+                self._staged_pairs().copy_(self._act[0:2].T)
             if self._graph is None:     # partner -> fused step (-> the partner's update), captured once
                 def one_step():
                     self._partner_and_step(self._ego_pairs)
@@ -995,7 +442,7 @@ class OvercookedVecEnv(_VecEnvBase):
         to which column of which dtype block (int64 / float32 / int8 as the declared spaces,
         overcooked_env.py:41-85), the device and pinned host buffers, and the numpy views' offsets."""
         b, n = self._b, self.num_envs
-        L = _lib.load_hostio()
+        L = _lib.load(lib="hostio")
         block_of = {np.dtype(np.int64): 0, np.dtype(np.float32): 1, np.dtype(np.int8): 2}
         width, plan, cols = [0, 0, 0], np.zeros(b.F, np.int32), {}
         for k, (lo, hi) in b._layout.items():
@@ -1017,7 +464,7 @@ class OvercookedVecEnv(_VecEnvBase):
                 "dev": torch.empty(max(total, 1), dtype=torch.uint8, device=b.device),
                 "pinned": [torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
                            for _ in range(2 if self._reuse_host else 1)], "off": off,
-                "ot": {torch.int32: 0, torch.int8: 1, torch.float32: 2}[b.obs.dtype]}
+                "ot": OBS_TYPE[b.obs.dtype]}
 
     def _host_step(self, rew=None, done=None):
         """Everything the numpy API returns for one step: ONE launch (``oc_pack_host``,
@@ -1030,13 +477,10 @@ class OvercookedVecEnv(_VecEnvBase):
         if hp is None:
             hp = self._host_plan_cache = self._host_plan()
         dp = lambda t: None if t is None else t.data_ptr()
-        with b._on_device():
-            rc = hp["L"].oc_pack_host(b.obs[0].data_ptr(), hp["ot"], b.F, hp["plan"].data_ptr(), hp["width"][0],
-                                      hp["width"][1], hp["width"][2], b.timestep.data_ptr(),
-                                      b.shaped_reward.data_ptr(), dp(b.ep_return), b.done.data_ptr(),
-                                      dp(b.ep_length), hp["dev"].data_ptr(), n, b._raw_stream())
-        if rc:
-            raise _lib.OcError("oc_pack_host failed (%d): %s" % (rc, hp["L"].oc_hostio_last_error().decode()))
+        _lib.call(hp["L"], "oc_pack_host", b._dev_index, b.obs[0].data_ptr(), hp["ot"], b.F, hp["plan"].data_ptr(),
+                  hp["width"][0], hp["width"][1], hp["width"][2], b.timestep.data_ptr(),
+                  b.shaped_reward.data_ptr(), dp(b.ep_return), b.done.data_ptr(), dp(b.ep_length),
+                  hp["dev"].data_ptr(), n)
         self._host_flip ^= 1
         pinned = hp["pinned"][self._host_flip if self._reuse_host else 0]
         pinned.copy_(hp["dev"], non_blocking=True)
@@ -1065,11 +509,10 @@ class OvercookedVecEnv(_VecEnvBase):
         # host actions -> pinned staging -> the device pairs the kernel consumes as they lie
         if self._act_pinned is None:
             self._act_pinned = torch.empty((self.num_envs, 2), dtype=torch.int32, pin_memory=True)
-            if self._ego_pairs is None:
-                self._ego_pairs = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self._b.device)
         np.copyto(self._act_pinned.numpy(), self._pending.reshape(self.num_envs, 2), casting="unsafe")
-        self._ego_pairs.copy_(self._act_pinned, non_blocking=True)
-        _, rew, done = self.step_tensors(self._ego_pairs)
+        ego_pairs = self._staged_pairs()
+        ego_pairs.copy_(self._act_pinned, non_blocking=True)
+        _, rew, done = self.step_tensors(ego_pairs)
         obs_np, rew_np, done_i32 = self._host_step(rew, done)
         done_np = done_i32.astype(bool)
         infos = self._infos                       # the same list every step (as DummyVecEnv's buf_infos)

@@ -93,11 +93,11 @@ def test_c_abi_exports_every_declared_symbol():
     build.build()
     hdr = open(os.path.join(ROOT, "include", "oc_hip.h")).read()
     declared = re.findall(r"OC_API\s+[\w\s\*]+?\b(oc_\w+)\s*\(", hdr)
-    assert sorted(declared) == sorted(_lib.SYMBOLS)
+    assert sorted(declared) == sorted(_lib.LIBS["hip"].protos)
     L = _lib.load()
     for sym in declared:
         assert getattr(L, sym) is not None
-    assert L.oc_abi_version() == _lib.ABI_VERSION == 6
+    assert L.oc_abi_version() == _lib.LIBS["hip"].abi_version == 6
     assert L.oc_timeline_begin(None, 0, 0) == -1 and b"timeline" in L.oc_last_error()    # the product build refuses
     # argument validation happens before any device work
     assert L.oc_step(None, None, None, None, None, None, 0, None, None, None, 0, None) == -1
@@ -131,14 +131,14 @@ def test_policy_library_exports_its_header_and_packs_fragments_as_documented():
     declares; the host-side packers put every weight where the header says the MFMA fragments
     expect it (an index-by-index restatement of the three layouts)."""
     from gym_comm_amd import _lib, build
-    build.build_policy()
+    build.build_lib("policy")
     hdr = open(os.path.join(ROOT, "include", "oc_policy.h")).read()
     declared = re.findall(r"OC_API\s+[\w\s\*]+?\b(oc_policy_\w+)\s*\(", hdr)
-    assert sorted(declared) == sorted(_lib.POLICY_SYMBOLS)
-    L = _lib.load_policy()
+    assert sorted(declared) == sorted(_lib.LIBS["policy"].protos)
+    L = _lib.load(lib="policy")
     for sym in declared:
         assert getattr(L, sym) is not None
-    assert L.oc_policy_abi_version() == _lib.POLICY_ABI_VERSION == 1
+    assert L.oc_policy_abi_version() == _lib.LIBS["policy"].abi_version == 1
     assert [L.oc_policy_ksteps(F) for F in (1, 14, 15, 29, 30, 31, 46, 47)] == [1, 1, 2, 2, 2, 3, 3, 4]
     rng = np.random.default_rng(5)
     fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
@@ -186,12 +186,12 @@ def test_hostio_library_exports_its_header():
     """liboc_hostio.so (include/oc_hostio.h: the numpy boundary's pack kernel) loads without a
     GPU, exports what its header declares, and sizes its buffer as documented."""
     from gym_comm_amd import _lib, build
-    build.build_hostio()
+    build.build_lib("hostio")
     hdr = open(os.path.join(ROOT, "include", "oc_hostio.h")).read()
     declared = re.findall(r"OC_API\s+[\w\s\*]+?\b(oc_\w+)\s*\(", hdr)
-    assert sorted(declared) == sorted(_lib.HOSTIO_SYMBOLS)
-    L = _lib.load_hostio()
-    assert L.oc_hostio_abi_version() == _lib.HOSTIO_ABI_VERSION == 1
+    assert sorted(declared) == sorted(_lib.LIBS["hostio"].protos)
+    L = _lib.load(lib="hostio")
+    assert L.oc_hostio_abi_version() == _lib.LIBS["hostio"].abi_version == 1
     n = 1000
     assert L.oc_pack_host_bytes(8, 4, 17, 1, 1, 1, 1, n) == n * (8 * 8 + 8 + 4 * 4 + 4 + 4 + 4 + 4 + 17)
     assert L.oc_pack_host_bytes(8, 4, 17, 0, 0, 0, 0, n) == n * (8 * 8 + 4 * 4 + 4 + 17)

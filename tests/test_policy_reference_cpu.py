@@ -17,8 +17,8 @@ import policy_ref  # noqa: E402
 
 def _policy_lib():
     from gym_comm_amd import _lib, build
-    build.build_policy()
-    return _lib.load_policy()
+    build.build_lib("policy")
+    return _lib.load(lib="policy")
 
 
 def _pcg32_scalar(s):

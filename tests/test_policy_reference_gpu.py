@@ -210,7 +210,7 @@ def test_nothing_is_written_past_n(monkeypatch):
     sentinel (two players, padding workgroups, a ragged last wave; both workgroup mappings)."""
     from gym_comm_amd import _lib
     from gym_comm_amd.vec_env import FusedMLPPartner
-    L = _lib.load_policy()
+    L = _lib.load(lib="policy")
     F, C, n, tail = 33, 6, 777, 4096
     SENT = -0x5A5A5A5B
     ts = _timesteps(n, 333, 1)

@@ -19,8 +19,8 @@ def _lib_and_buf(**over):
     """The typed library and a buffer description whose pointers are non-NULL but never
     dereferenced (argument errors come before any device call)."""
     from gym_comm_amd import _lib, build
-    build.build_rollout()
-    L = _lib.load_rollout()
+    build.build_lib("rollout")
+    L = _lib.load(lib="rollout")
     fields = dict((name, 0x1000) for name, _ in _lib.RolloutBuf._fields_[:14])
     fields.update(n=64, T=4, F=3, obs_type=0)
     fields.update(over)
@@ -37,17 +37,17 @@ def _calls(L, buf):
 
 def test_rollout_library_exports_its_header():
     from gym_comm_amd import _lib, build
-    lib = build.build_rollout()
+    lib = build.build_lib("rollout")
     assert os.path.exists(lib) and os.path.basename(lib) == "liboc_rollout.so"
-    assert os.path.dirname(lib) == os.path.dirname(build.HOSTIO_LIB)
+    assert os.path.dirname(lib) == os.path.dirname(build.LIBS["hostio"].lib)
     hdr = open(os.path.join(ROOT, "include", "oc_rollout.h")).read()
     declared = re.findall(r"OC_API\s+[\w\s\*]+?\b(oc_\w+)\s*\(", hdr)
-    assert sorted(declared) == sorted(_lib.ROLLOUT_SYMBOLS)
-    L = _lib.load_rollout()
-    for sym in _lib.ROLLOUT_SYMBOLS:
+    assert sorted(declared) == sorted(_lib.LIBS["rollout"].protos)
+    L = _lib.load(lib="rollout")
+    for sym in _lib.LIBS["rollout"].protos:
         getattr(L, sym)
     version = int(re.search(r"#define OC_ROLLOUT_ABI_VERSION (\d+)", hdr).group(1))
-    assert L.oc_rollout_abi_version() == _lib.ROLLOUT_ABI_VERSION == version
+    assert L.oc_rollout_abi_version() == _lib.LIBS["rollout"].abi_version == version == 1
     # the ctypes struct has the header's fields, in order
     body = re.search(r"typedef struct \{(.*?)\} oc_rollout_buf;", hdr, re.S).group(1)
     names = re.findall(r"(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
@@ -85,7 +85,7 @@ def test_rollout_kernels_have_no_private_segment(tmp_path):
     tools = "/opt/rocm/lib/llvm/bin/"
     if not all(os.path.exists(tools + t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")):
         pytest.skip("llvm binary tools not available")
-    so = build.build_rollout()
+    so = build.build_lib("rollout")
     fat, co = str(tmp_path / "f.bin"), str(tmp_path / "k.co")
     subprocess.run([tools + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, so], check=True)
     subprocess.run([tools + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat,
