@@ -48,6 +48,12 @@ class PolicyPlayer(ctypes.Structure):
                 ("logits", ctypes.c_void_p)]
 
 
+class PolicyAcPlayer(ctypes.Structure):
+    """oc_policy_ac_player (include/oc_policy.h)."""
+    _fields_ = [("p", PolicyPlayer), ("given", ctypes.c_void_p), ("move_row", ctypes.c_void_p),
+                ("comm_row", ctypes.c_void_p), ("log_prob", ctypes.c_void_p), ("value", ctypes.c_void_p)]
+
+
 class RolloutBuf(ctypes.Structure):
     """oc_rollout_buf (include/oc_rollout.h)."""
     _fields_ = [(name, ctypes.c_void_p) for name in
@@ -105,6 +111,9 @@ def _libs_table():
             "oc_policy_pack_w2": (cint, [fp, i32, vp]),
             "oc_policy_pack_b2": (cint, [fp, fp, i32, fp]),
             "oc_policy_mlp": (cint, [P(PolicyPlayer), i32, vp, i32, i32, i32, i64, vp]),
+            "oc_policy_pack_w2v": (cint, [fp, fp, i32, vp]),
+            "oc_policy_pack_b2v": (cint, [fp, fp, fp, fp, i32, fp]),
+            "oc_policy_mlp_ac": (cint, [P(PolicyAcPlayer), i32, vp, i32, i32, i32, i64, vp]),
         }),
         "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
             "oc_hostio_abi_version": (cint, None),

@@ -11,6 +11,7 @@
 
 #include "../../include/oc_policy.h"
 #include "oc_policy_device.h"
+#include "oc_policy_ac_device.h"
 
 namespace {
 
@@ -47,6 +48,31 @@ __global__ void __launch_bounds__(64 * WPB) k_policy_mlp(const Args p, const int
   const int64_t env = valid ? env0 : p.n - 1;   // lanes past the batch compute on the last env, store nothing
   policy_pass<OT, CMAX>(P.obs, (uint32_t)p.n, (uint32_t)env, valid, lane, P.w1, P.w2, P.b2, P.rng, P.pairs, P.logits,
                         (float)p.timestep[env], p.F, p.C, p.ksteps);
+}
+
+// The actor-critic launch (oc_policy_mlp_ac): k_policy_mlp's grid and mapping, the tail of
+// oc_policy_ac_device.h behind the same two products.
+struct AcArgs {
+  oc_policy_ac_player pl[2];
+  const double *timestep;
+  int32_t F, C, ksteps;
+  int64_t n;
+};
+
+template <int OT, int WPB, int CMAX>
+__global__ void __launch_bounds__(64 * WPB) k_policy_mlp_ac(const AcArgs p, const int gx, const int gx8) {
+  const int x = (int)(blockIdx.x % (unsigned)gx8), y = (int)(blockIdx.x / (unsigned)gx8);
+  if (x >= gx) return;                       // padding workgroup (uniform)
+  const oc_policy_ac_player &A = p.pl[y];
+  const oc_policy_player &P = A.p;
+  const int lane = threadIdx.x & 63, r = lane & 31;
+  const int64_t env0 = ((int64_t)x * WPB + (threadIdx.x >> 6)) * 32 + r;
+  const bool valid = env0 < p.n;
+  const int64_t env = valid ? env0 : p.n - 1;   // lanes past the batch compute on the last env, store nothing
+  const AcTail tail = {A.given, A.move_row, A.comm_row, A.log_prob, A.value};
+  policy_pass<OT, CMAX, false, false, AcTail>(P.obs, (uint32_t)p.n, (uint32_t)env, valid, lane, P.w1, P.w2, P.b2, P.rng,
+                                              P.pairs, P.logits, (float)p.timestep[env], p.F, p.C, p.ksteps, nullptr,
+                                              0, nullptr, &tail);
 }
 
 uint16_t f32_to_f16_bits(float f) {   // round to nearest even, host side
@@ -117,6 +143,76 @@ int oc_policy_pack_b2(const float *b2, const float *w2, int32_t C, float *out) {
       }
       out[l * 16 + r] = v;
     }
+  return 0;
+}
+
+// The value head rides in row 8 of the second product (register 4 of the lower half-wave's lanes),
+// folded exactly as a logit row is; every other element is oc_policy_pack_w2's / _b2's.
+int oc_policy_pack_w2v(const float *w2, const float *wv, int32_t C, uint16_t *out) {
+  if (!wv) return fail("oc_policy_pack_w2v: bad argument (wv)");
+  if (oc_policy_pack_w2(w2, C, out) != 0) return -1;
+  for (int s = 0; s < 4; s++)
+    for (int l = 8; l < 64; l += 32)
+      for (int j = 0; j < 8; j++) {
+        const int hid = 16 * s + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3);
+        out[((size_t)s * 64 + l) * 8 + j] = f32_to_f16_bits(w2_folded(wv, 0, hid));
+      }
+  return 0;
+}
+
+int oc_policy_pack_b2v(const float *b2, const float *w2, const float *bv, const float *wv, int32_t C, float *out) {
+  if (!bv || !wv) return fail("oc_policy_pack_b2v: bad argument (bv, wv)");
+  if (oc_policy_pack_b2(b2, w2, C, out) != 0) return -1;
+  float sum = 0.0f;
+  for (int j = 0; j < OC_POLICY_HIDDEN; j++) sum += w2_folded(wv, 0, j);
+  for (int l = 0; l < 32; l++) out[l * 16 + 4] = ocpol::K_LOG2E * bv[0] - 0.5f * sum;
+  return 0;
+}
+
+int oc_policy_mlp_ac(const oc_policy_ac_player *players, int32_t num_players, const double *timestep, int32_t F,
+                     int32_t C, int32_t obs_type, int64_t n, void *stream) {
+  if (!players || num_players < 1 || num_players > 2 || !timestep || F < 1 || C < 1 || C > OC_POLICY_MAX_COMM ||
+      obs_type < 0 || obs_type > 2 || n < 0)
+    return fail("oc_policy_mlp_ac: bad argument (1..2 players, 1 <= C <= 16, obs_type 0..2)");
+  AcArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int k = 0; k < num_players; k++) {
+    if (!players[k].p.obs || !players[k].p.w1 || !players[k].p.w2 || !players[k].p.b2)
+      return fail("oc_policy_mlp_ac: a player needs obs, w1, w2 and b2");
+    if (!players[k].move_row != !players[k].comm_row)
+      return fail("oc_policy_mlp_ac: move_row and comm_row are given together");
+    a.pl[k] = players[k];
+  }
+  if (n == 0) return 0;
+  if ((int64_t)F * n >= ((int64_t)1 << 31)) return fail("oc_policy_mlp_ac: F * n must stay below 2^31; split the batch");
+  a.timestep = timestep;
+  a.F = F, a.C = C, a.ksteps = oc_policy_ksteps(F), a.n = n;
+  const char *ev = getenv("OC_POLICY_WG32");   // as oc_policy_mlp
+  const int wpb = (ev && ev[0] == '1') ? 1 : 2;
+  const int64_t gx = (n + 32 * wpb - 1) / (32 * wpb), gx8 = (gx + 7) / 8 * 8;
+  if (gx8 * num_players > 0x7FFFFFFF) return fail("oc_policy_mlp_ac: n too large");
+  const dim3 g((unsigned)(gx8 * num_players)), b(64 * wpb);
+#define OC_PL2(OT_, CM_)                                                                                    \
+  do {                                                                                                      \
+    if (wpb == 2) hipLaunchKernelGGL((k_policy_mlp_ac<OT_, 2, CM_>), g, b, 0, (hipStream_t)stream, a, (int)gx, (int)gx8); \
+    else hipLaunchKernelGGL((k_policy_mlp_ac<OT_, 1, CM_>), g, b, 0, (hipStream_t)stream, a, (int)gx, (int)gx8); \
+  } while (0)
+#define OC_PL(OT_)                 \
+  do {                             \
+    if (C <= 4) OC_PL2(OT_, 4);    \
+    else if (C <= 8) OC_PL2(OT_, 8); \
+    else OC_PL2(OT_, 16);          \
+  } while (0)
+  if (obs_type == 1) OC_PL(1);
+  else if (obs_type == 2) OC_PL(2);
+  else OC_PL(0);
+#undef OC_PL2
+#undef OC_PL
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(g_err, sizeof(g_err), "oc_policy_mlp_ac: kernel launch: %s", hipGetErrorString(e));
+    return (int)e;
+  }
   return 0;
 }
 

@@ -127,12 +127,21 @@ __device__ __forceinline__ void load_weights(Weights &w, const uint16_t *w1_, co
 //   LDSSRC: the features come from an LDS image instead -- `lds` float [F][64] (one column per env
 //   of the workgroup), this lane's column `col` -- as the fused step kernel hands them over
 //   PRE: the weights are already in registers (`pre`, load_weights), ksteps <= MAX_KSTEPS
-template <int OT, int CMAX, bool LDSSRC = false, bool PRE = false>
+// The pass has two parts: both products, up to the second one's 16 accumulator registers `out`, and
+// "sample and store".  A caller may put its own second part behind the first: with a `Tail` type
+//   tail->template run<CMAX>(out, n32, env, valid, lane, rng, pairs, logits, C)
+// takes the place of the sampler and the stores below (the actor-critic kernel does,
+// oc_policy_ac_device.h).  The parts are cut at compile time inside ONE function body on purpose:
+// as two functions the compiler simplifies each before it inlines them, and the step kernel's POL
+// variants came out with other addressing and register allocation; like this every caller
+// without a tail compiles to the instructions it had before the cut.
+struct NoTail {};
+template <int OT, int CMAX, bool LDSSRC = false, bool PRE = false, class Tail = NoTail>
 __device__ __forceinline__ void policy_pass(const void *obs, uint32_t n32, uint32_t env, bool valid, int lane,
                                             const uint16_t *w1_, const uint16_t *w2_, const float *b2_,
                                             uint32_t *rng, int32_t *pairs, float *logits, float ts, int F,
                                             int C, int ksteps, const float *lds = nullptr, int col = 0,
-                                            const Weights *pre = nullptr) {
+                                            const Weights *pre = nullptr, const Tail *tail = nullptr) {
   const int h = lane >> 5;
   // ---- H^T = W1aug . X^T ---------------------------------------------------------------
   f32x16 acc0, acc1;
@@ -189,20 +198,24 @@ __device__ __forceinline__ void policy_pass(const void *obs, uint32_t n32, uint3
     out = __builtin_amdgcn_mfma_f32_32x32x16_f16(PRE ? pre->w2[s] : w2[s * 64 + lane], b, out, 0, 0, 0);
   }
 
-  // ---- sample and store ------------------------------------------------------------------
-  // lower half-wave: move of env r from registers 0..3; upper: comm of env r from registers 0..C-1
-  const int count = h ? C : 4;
-  const bool sample = rng != nullptr;
-  uint32_t state = 0;
-  if (sample) state = rng[(size_t)h * n32 + env];
-  const int choice = pick<CMAX>(out, count, sample, state);
-  if (valid) {
-    pairs[(size_t)env * 2 + h] = choice;
-    if (sample) rng[(size_t)h * n32 + env] = state;
-    if (logits != nullptr) {
+  if constexpr (!__is_same(Tail, NoTail)) {
+    tail->template run<CMAX>(out, n32, env, valid, lane, rng, pairs, logits, C);
+  } else {
+    // ---- sample and store ------------------------------------------------------------------
+    // lower half-wave: move of env r from registers 0..3; upper: comm of env r from registers 0..C-1
+    const int count = h ? C : 4;
+    const bool sample = rng != nullptr;
+    uint32_t state = 0;
+    if (sample) state = rng[(size_t)h * n32 + env];
+    const int choice = pick<CMAX>(out, count, sample, state);
+    if (valid) {
+      pairs[(size_t)env * 2 + h] = choice;
+      if (sample) rng[(size_t)h * n32 + env] = state;
+      if (logits != nullptr) {
 #pragma unroll
-      for (int c = 0; c < CMAX; c++)
-        if (c < count) logits[(size_t)((h ? 4 : 0) + c) * n32 + env] = out[c] * K_LN2;   // natural-log logits
+        for (int c = 0; c < CMAX; c++)
+          if (c < count) logits[(size_t)((h ? 4 : 0) + c) * n32 + env] = out[c] * K_LN2;   // natural-log logits
+      }
     }
   }
 }

@@ -1,5 +1,6 @@
 """The players an ``OvercookedVecEnv`` seats (see ``vec_env`` for the overview): ``RandomPartner``,
-``MLPPolicy``, ``TorchPolicyPartner``, ``RecurrentPolicyPartner``, ``FusedMLPPartner``."""
+``MLPPolicy``, ``MLPActorCritic``, ``TorchPolicyPartner``, ``RecurrentPolicyPartner``, ``FusedMLPPartner``,
+``FusedActorCriticPartner``."""
 import ctypes
 
 import numpy as np
@@ -89,16 +90,39 @@ class MLPPolicy(torch.nn.Module):
         self.w1, self.b1, self.wt = init(hidden, F), init(hidden, 1), init(hidden, 1)
         self.w2, self.b2 = init(4 + int(num_comm), hidden), init(4 + int(num_comm), 1)
         self.C = int(num_comm)
+        self._more_parameters(init, hidden)
 
-    def forward(self, obs):
+    def _more_parameters(self, init, hidden):
+        """A subclass draws its own parameters here: from the same generator, after these."""
+
+    def _hidden(self, obs):
+        """tanh of the first layer, [H][n]."""
         rows, ts = rows_and_timestep(obs)
         ts = ts.unsqueeze(0)
         if rows.dtype != torch.float32:
             rows = rows.to(torch.float32)
         h = torch.addmm(self.b1, self.w1, rows)                 # [H][n]
         h = torch.addcmul(h, self.wt, ts.to(torch.float32))
-        out = torch.addmm(self.b2, self.w2, torch.tanh_(h))     # [4 + C][n]
+        return torch.tanh_(h)
+
+    def forward(self, obs):
+        out = torch.addmm(self.b2, self.w2, self._hidden(obs))  # [4 + C][n]
         return out[:4], out[4:]
+
+
+class MLPActorCritic(MLPPolicy):
+    """``MLPPolicy`` with a value head on the same hidden layer: ``value = wv . tanh(h) + bv``.  The
+    head's parameters are drawn after the parent's, so ``MLPActorCritic(S, C, seed=s)`` carries the
+    policy weights of ``MLPPolicy(S, C, seed=s)``; ``forward`` is the parent's."""
+
+    def _more_parameters(self, init, hidden):
+        self.wv, self.bv = init(1, hidden), init(1, 1)
+
+    def forward_ac(self, obs):
+        """(move logits [4][n], comm logits [C][n], value [n])."""
+        h = self._hidden(obs)
+        out = torch.addmm(self.b2, self.w2, h)                  # [4 + C][n]
+        return out[:4], out[4:], torch.addmm(self.bv, self.wv, h).reshape(-1)
 
 
 class TorchPolicyPartner(_Seat):
@@ -369,3 +393,158 @@ class FusedMLPPartner:
     def set_state(self, st):
         self._rng.copy_(st[0])
         self.pairs.copy_(st[1])
+
+
+class FusedActorCriticPartner(_Seat):
+    """An ``MLPActorCritic`` in the seat of a player that LEARNS, as ONE launch of the policy kernel's
+    actor-critic form (include/oc_policy.h: ``oc_policy_mlp_ac``): what ``OnPolicyAgent.get_action``
+    takes from its forward (pantheonrl/common/agents.py:112-194) -- the sampled action, written into
+    the env's action rows as they lie, its log-probability and the state's value -- and, with a
+    ``sink`` (a ``RolloutSink``), the recording of the step behind it.  The value head rides in a row
+    of the second matrix product that no logit uses; the log-probability comes from the softmax
+    normaliser the sampler forms anyway.
+
+    The seat protocol is ``RecurrentPolicyPartner``'s: ``act_into``, ``update(rewards, dones)``
+    (``dones`` become the next step's ``episode_start``, the reward joins the recorded step),
+    ``reset()``, ``finish_rollout()``.  Not a ``FusedMLPPartner``: the paths ``vec_env`` gives that
+    class (pairs consumed as they lie, the step kernel evaluating the policy itself) produce
+    neither value nor log-probability.  ``score(obs, pairs)`` evaluates GIVEN actions: what a
+    learner's update needs."""
+    graph_safe = True
+
+    def __init__(self, policy, sample=True, seed=None, device="cuda", sink=None, keep_logits=False):
+        if seed is None:        # as FusedMLPPartner: seats left at their defaults never share streams
+            seed = 0x5EED + 1000003 * FusedMLPPartner._seats
+        FusedMLPPartner._seats += 1
+        if not isinstance(policy, MLPActorCritic):
+            raise TypeError("FusedActorCriticPartner runs gym_comm_amd.vec_env.MLPActorCritic")
+        if policy.w1.shape[0] != 64:
+            raise ValueError("the fused kernel has 64 hidden units (got %d)" % policy.w1.shape[0])
+        if not 1 <= policy.C <= 16:
+            raise ValueError("the fused kernel samples at most 16 comm channels (got %d)" % policy.C)
+        self.policy, self.sample, self.seed = policy, bool(sample), int(seed)
+        self.device = torch.device(device)
+        self.sink = sink
+        self.keep_logits = bool(keep_logits)
+        self._L = _lib.load(lib="policy")
+        self.F = int(policy.w1.shape[1])
+        self.C = int(policy.C)
+        self._w = None
+        self._rng = self.episode_start = self.log_prob = self.value = self.logits = None
+        self.refresh()
+
+    def refresh(self):
+        """(Re)pack the module's current weights, value row included, and upload them."""
+        L, pol = self._L, self.policy
+        f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+        fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        ks = L.oc_policy_ksteps(self.F)
+        w1, wt, b1, w2, b2, wv, bv = (f32(t) for t in (pol.w1, pol.wt, pol.b1, pol.w2, pol.b2, pol.wv, pol.bv))
+        o1 = np.zeros((2, ks, 64, 8), np.uint16)
+        o2 = np.zeros((4, 64, 8), np.uint16)
+        ob = np.zeros((64, 16), np.float32)
+        for rc, what in ((L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), self.F,
+                                              o1.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w1"),
+                         (L.oc_policy_pack_w2v(fp(w2), fp(wv.reshape(-1)), self.C, o2.ctypes.data_as(ctypes.c_void_p)),
+                          "oc_policy_pack_w2v"),
+                         (L.oc_policy_pack_b2v(fp(b2.reshape(-1)), fp(w2), fp(bv.reshape(-1)), fp(wv.reshape(-1)),
+                                               self.C, fp(ob)), "oc_policy_pack_b2v")):
+            _lib.check(rc, what, L)
+        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
+                    for a in (o1, o2, ob))
+        if self._w is None:
+            self._w = new
+        else:                       # in place: a captured graph keeps the addresses
+            for old, cur in zip(self._w, new):
+                old.copy_(cur)
+
+    def _buffers(self, n):
+        if self.log_prob is None or self.log_prob.numel() != n:
+            dev = self.device
+            self._rng = pcg32_seed_states(self.seed, (2, n), dev)
+            self.episode_start = torch.ones(n, dtype=torch.float32, device=dev)
+            self.log_prob = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.value = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.logits = torch.zeros((4 + self.C, n), dtype=torch.float32, device=dev) if self.keep_logits else None
+
+    def _launch(self, rows, timestep, given, move_row, comm_row, log_prob, value):
+        n = rows.shape[1]
+        if rows.shape[0] != self.F:
+            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
+        if not rows.is_contiguous():
+            raise ValueError("the kernel reads the observation rows as they lie: [F][n], contiguous")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        use_rng = self.sample and given is None
+        pl = _lib.PolicyAcPlayer(
+            _lib.PolicyPlayer(rows.data_ptr(), self._w[0].data_ptr(), self._w[1].data_ptr(), self._w[2].data_ptr(),
+                              self._rng.data_ptr() if use_rng else None, None,
+                              ptr(self.logits) if given is None else None),
+            ptr(given), ptr(move_row), ptr(comm_row), ptr(log_prob), ptr(value))
+        _lib.call(self._L, "oc_policy_mlp_ac", rows.device.index, ctypes.byref(pl), 1, timestep.data_ptr(),
+                  self.F, self.C, OBS_TYPE[rows.dtype], n)
+
+    @staticmethod
+    def _action_row(t, n):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError("an action row is a contiguous int32 tensor of %d elements" % n)
+        return t
+
+    def act_into(self, obs, move_row, comm_row):
+        """ONE launch: the actions into ``move_row`` / ``comm_row`` (the env's own rows, no copy),
+        ``self.log_prob`` and ``self.value``; then the sink's ``add``."""
+        rows, ts = rows_and_timestep(obs)
+        n = rows.shape[1]
+        self._buffers(n)
+        self._launch(rows, ts, None, self._action_row(move_row, n), self._action_row(comm_row, n),
+                     self.log_prob, self.value)
+        if self.sink is not None:
+            self.sink.add(rows, ts, move_row, comm_row, self.log_prob, self.value, self.episode_start)
+
+    def score(self, obs, pairs):
+        """(log_prob [n], value [n]) of GIVEN actions, int32 [n][2] (move, comm), under the current
+        weights: one launch, fresh tensors.  n is the scored batch's own (a minibatch of recorded
+        rows, say), whatever the seat's: none of the seat's state -- streams, ``episode_start``,
+        ``log_prob``, ``value``, kept logits -- is read, written or reallocated.  An index outside
+        its head's range yields -inf."""
+        rows, ts = rows_and_timestep(obs)
+        n = rows.shape[1]
+        if pairs.dtype != torch.int32 or tuple(pairs.shape) != (n, 2) or not pairs.is_contiguous():
+            raise ValueError("pairs: a contiguous int32 [%d][2] tensor" % n)
+        lp = torch.empty(n, dtype=torch.float32, device=rows.device)
+        val = torch.empty(n, dtype=torch.float32, device=rows.device)
+        self._launch(rows, ts, pairs, None, None, lp, val)
+        return lp, val
+
+    def reset(self):
+        """A fresh rollout: every env starts an episode (called by ``reset_tensors``)."""
+        if self.episode_start is not None:
+            self.episode_start.fill_(1.0)
+
+    def update(self, rewards, dones):
+        """pantheonrl's ``Agent.update(reward, done)`` for the batch (``RecurrentPolicyPartner.update``)."""
+        self._buffers(dones.numel())
+        self.episode_start.copy_(dones)
+        if self.sink is not None:
+            self.sink.add_reward(rewards, dones)
+
+    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
+        """``RecurrentPolicyPartner.finish_rollout``: the sink's (advantages, returns) with the values
+        of the last ``act_into`` and the last ``done`` row; the sink is not reset."""
+        if self.sink is None:
+            raise ValueError("finish_rollout needs a sink")
+        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
+
+    def get_state(self, n):
+        """The seat's mutable state: its random streams, ``episode_start``, the last ``log_prob`` /
+        ``value`` and the sink's position."""
+        self._buffers(n)
+        return (self._rng.clone(), self.episode_start.clone(), self.log_prob.clone(), self.value.clone(),
+                None if self.sink is None else self.sink.get_state())
+
+    def set_state(self, st):
+        self._rng.copy_(st[0])
+        self.episode_start.copy_(st[1])
+        self.log_prob.copy_(st[2])
+        self.value.copy_(st[3])
+        if self.sink is not None:
+            self.sink.set_state(st[4])

@@ -51,8 +51,8 @@ import torch
 from . import _lib
 from .batched import BatchedOvercooked, OBS_TYPE
 from .envs import OvercookedEnvironment, _arg, make_spaces
-from .partners import (FusedMLPPartner, MLPPolicy, RandomPartner,  # noqa: F401 (re-exported)
-                       RecurrentPolicyPartner, TorchPolicyPartner)
+from .partners import (FusedActorCriticPartner, FusedMLPPartner, MLPActorCritic, MLPPolicy,  # noqa: F401 (re-exported)
+                       RandomPartner, RecurrentPolicyPartner, TorchPolicyPartner)
 from .rollout import RolloutSink  # noqa: F401 (re-exported)
 
 try:                                                    # pragma: no cover - SB3 absent in CI image

@@ -83,6 +83,52 @@ OC_API int oc_policy_pack_b2(const float *b2, const float *w2, int32_t C, float 
 OC_API int oc_policy_mlp(const oc_policy_player *players, int32_t num_players, const double *timestep,
                          int32_t F, int32_t C, int32_t obs_type, int64_t n, void *stream);
 
+/* ---- the actor-critic form: the same network with a value head, for a player that learns ----
+ *
+ * What OnPolicyAgent.get_action needs of its one forward per step (pantheonrl/common/agents.py:
+ * 112-194): the action, its log-probability under the policy and the state's value.
+ *     value    = wv . tanh(W1 x + wt * timestep + b1) + bv       on the same 64 hidden units
+ *     log_prob = ln softmax(logits[0:4])[move] + ln softmax(logits[4:4+C])[comm]
+ * for the (move, comm) that is written -- sampled, greedy, or GIVEN (`given`: score these actions
+ * instead of choosing, what a learner's update evaluates).
+ *
+ * The value head is row 8 of the second product, a row no logit uses: register 4 of the lower
+ * half-wave's lanes.  It is folded exactly as a logit row is -- -2 log2(e) wv in fp16 at element j
+ * of lanes 8 and 40 (h = l >> 5) of k-step s = hidden unit 16 s + 8 (j >> 2) + 4 h + (j & 3), and
+ * the start value log2(e) bv - 1/2 sum_j (rounded weights) in register 4 of lanes 0..31 -- and the
+ * kernel reads it back as out[4] * ln 2.  oc_policy_pack_w2v / _b2v produce oc_policy_pack_w2's /
+ * _b2's output with that row filled in: every other element is the same.
+ *
+ * The log-probability, per head, in float32 and in this order, with the head's base-2 logits L_c
+ * (c = 0 .. count-1 in candidate order), a the action:
+ *     m = max_c L_c;   e_c = 2^(L_c - m);   S = sum_c e_c   (from 0, c ascending: the sampler's own total)
+ *     lp = ((L_a - m) - log2 S) * ln 2          (v_exp_f32, v_log_f32; ln 2 the float 0.6931471805599453f)
+ *     log_prob = lp_move + lp_comm
+ * A `given` index outside its head's range makes log_prob -inf for that env and touches nothing
+ * else (it is echoed into pairs / move_row / comm_row where those are asked for).
+ * For the same packed logit rows, observations and stream states, pairs, logits and the advanced
+ * streams are bit for bit oc_policy_mlp's. */
+typedef struct {
+  oc_policy_player p;     /* obs, w1, w2, b2, rng, pairs, logits as above; pairs may be NULL here;
+                             w2 / b2 packed WITH the value row (oc_policy_pack_w2v / _b2v) */
+  const int32_t *given;   /* optional int32 [n][2]: score THESE (move, comm) instead of choosing;
+                             p.rng is then neither read nor advanced */
+  int32_t *move_row;      /* optional out, int32 [n] */
+  int32_t *comm_row;      /* optional out, int32 [n]; given together with move_row */
+  float *log_prob;        /* optional out, float [n] */
+  float *value;           /* optional out, float [n] */
+} oc_policy_ac_player;
+
+/* Host-side packing with the value row.  w2, b2 as for oc_policy_pack_w2 / _b2; wv [64], bv [1]. */
+OC_API int oc_policy_pack_w2v(const float *w2, const float *wv, int32_t C, uint16_t *out);
+OC_API int oc_policy_pack_b2v(const float *b2, const float *w2, const float *bv, const float *wv,
+                              int32_t C, float *out);
+
+/* One launch, as oc_policy_mlp (same arguments, grid and checks): lane l < 32 of a wave stores
+ * log_prob, value and move_row of its env, lane l + 32 comm_row. */
+OC_API int oc_policy_mlp_ac(const oc_policy_ac_player *players, int32_t num_players, const double *timestep,
+                            int32_t F, int32_t C, int32_t obs_type, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
