@@ -125,6 +125,7 @@ def _libs_table():
             "oc_rollout_abi_version": (cint, None),
             "oc_rollout_last_error": (cstr, None),
             "oc_rollout_add": (cint, [bp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "oc_rollout_add_plan": (cint, [bp, P(i32)]),
             "oc_rollout_add_reward": (cint, [bp, vp, vp, vp]),
             "oc_rollout_gae": (cint, [bp, vp, vp, ctypes.c_double, ctypes.c_double, vp]),
         }),

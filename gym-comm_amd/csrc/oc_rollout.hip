@@ -256,6 +256,26 @@ int check_buf(const char *fn, const oc_rollout_buf *b) {
   return 0;
 }
 
+// oc_rollout_add's launch: gridDim.x workgroup columns over the env blocks, `groups` rows of
+// `per_group` consecutive tasks each.
+// Launch- and latency-bound at a few thousand envs: a lone wave storing all F + 7 rows back to back
+// pays every store's issue in series, so the rows are dealt over ~512 workgroups (two per CU).  Never
+// more: each workgroup ends in one add on ONE word, which serves ~88 of them per microsecond.
+struct AddPlan {
+  int32_t gx, groups, per_group;
+};
+AddPlan add_plan(const oc_rollout_buf *buf) {
+  const int tasks = buf->F + TASK_EXTRA, target = 512;
+  const int64_t env_blocks = (buf->n + 255) / 256;
+  int groups = (int)((target + env_blocks - 1) / env_blocks);
+  groups = groups < 1 ? 1 : (groups > tasks ? tasks : groups);
+  const int per_group = (tasks + groups - 1) / groups;
+  groups = (tasks + per_group - 1) / per_group;
+  int64_t gx = target / groups;
+  gx = gx < 1 ? 1 : (gx > env_blocks ? env_blocks : gx);
+  return AddPlan{(int32_t)gx, groups, per_group};
+}
+
 }  // namespace
 
 extern "C" {
@@ -278,21 +298,21 @@ int oc_rollout_add(const oc_rollout_buf *buf, const void *rows, const double *ti
   a.rows = rows, a.ts = timestep, a.move = move, a.comm = comm, a.log_prob = log_prob, a.value = value;
   a.es = episode_start;
   a.n = (uint32_t)buf->n, a.T = buf->T, a.F = buf->F;
-  // Launch- and latency-bound at a few thousand envs: a lone wave storing all F + 7 rows back to back
-  // pays every store's issue in series, so the rows are dealt over ~512 workgroups (two per CU).  Never
-  // more: each workgroup ends in one add on ONE word, which serves ~88 of them per microsecond.
-  const int tasks = buf->F + TASK_EXTRA, target = 512;
-  const int64_t env_blocks = (buf->n + 255) / 256;
-  int groups = (int)((target + env_blocks - 1) / env_blocks);
-  groups = groups < 1 ? 1 : (groups > tasks ? tasks : groups);
-  a.per_group = (tasks + groups - 1) / groups;
-  groups = (tasks + a.per_group - 1) / a.per_group;
-  int64_t gx = target / groups;
-  gx = gx < 1 ? 1 : (gx > env_blocks ? env_blocks : gx);
-  const dim3 g((unsigned)gx, (unsigned)groups), b(256);
+  const AddPlan plan = add_plan(buf);
+  a.per_group = plan.per_group;
+  const dim3 g((unsigned)plan.gx, (unsigned)plan.groups), b(256);
   if (buf->obs_type == 1) hipLaunchKernelGGL(k_rollout_add<int8_t>, g, b, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_rollout_add<int32_t>, g, b, 0, (hipStream_t)stream, a);   // float32 rows: the same bits
   return launched(fn);
+}
+
+int oc_rollout_add_plan(const oc_rollout_buf *buf, int32_t plan[3]) {
+  static const char fn[] = "oc_rollout_add_plan";
+  if (const int rc = check_buf(fn, buf)) return rc;
+  if (!plan) return fail(fn, "NULL plan");
+  const AddPlan p = add_plan(buf);
+  plan[0] = p.gx, plan[1] = p.groups, plan[2] = p.per_group;
+  return 0;
 }
 
 int oc_rollout_add_reward(const oc_rollout_buf *buf, const double *rewards, const int32_t *dones, void *stream) {

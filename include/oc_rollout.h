@@ -81,6 +81,9 @@ OC_API int oc_rollout_add(const oc_rollout_buf *buf, const void *rows, const dou
                           const int32_t *move, const int32_t *comm, const float *log_prob,
                           const float *value /* may be NULL */, const float *episode_start, void *stream);
 
+/* No device work: the launch oc_rollout_add would make on `buf`, plan = {gridDim.x, groups, per_group}. */
+OC_API int oc_rollout_add_plan(const oc_rollout_buf *buf, int32_t plan[3]);
+
 /* ONE launch: rewards[*last] += rewards, dones[*last] = dones. */
 OC_API int oc_rollout_add_reward(const oc_rollout_buf *buf, const double *rewards, const int32_t *dones,
                                  void *stream);

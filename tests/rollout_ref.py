@@ -13,20 +13,24 @@ stable-baselines3's ``RolloutBuffer.compute_returns_and_advantage`` over CHRONOL
 ``gae(..., dtype=np.float32)`` rounds every operation to float32 in exactly that order (rewards
 are rounded to float32 first, g = float32(gamma), gl = float32(gamma * gae_lambda) with the product
 in double); ``dtype=np.float64`` is the same loop without any rounding to float32.
+
+``add_plan(n, F)`` restates how ``oc_rollout_add`` shapes its launch (csrc/oc_rollout.hip), from that
+file's description of it, for the CPU tests of ``oc_rollout_add_plan``.
 """
 import numpy as np
 
 
-def gae(rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda, dtype=np.float32):
+def gae(rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda, dtype=np.float32, gl=None):
     """rewards, values, episode_starts: [L][n]; last_values, last_dones: [n].  Returns
-    (advantages, returns), [L][n] of ``dtype``."""
+    (advantages, returns), [L][n] of ``dtype``.  ``gl`` replaces the discount of ``last`` (a test's
+    planted mutant: the product formed some other way)."""
     dt = np.dtype(dtype).type
     r = np.asarray(rewards, dtype=np.float64).astype(dt)
     v = np.asarray(values).astype(dt)
     es = np.asarray(episode_starts).astype(dt)
     L = r.shape[0]
     g = dt(np.float64(gamma))
-    gl = dt(np.float64(gamma) * np.float64(gae_lambda))
+    gl = dt(np.float64(gamma) * np.float64(gae_lambda)) if gl is None else dt(gl)
     one = dt(1)
     adv, ret = np.zeros_like(v), np.zeros_like(v)
     nv = np.asarray(last_values).astype(dt)
@@ -40,6 +44,27 @@ def gae(rewards, values, episode_starts, last_values, last_dones, gamma, gae_lam
         ret[k] = last + v[k]
         nv, nnt = v[k], one - es[k]
     return adv, ret
+
+
+def add_plan(n, F, target=512, block=256):
+    """(gridDim.x, groups, per_group) of ``oc_rollout_add``: a slot is F + 7 row tasks; with
+    ``ceil(n / 256)`` blocks of envs, enough groups of tasks to bring the launch to about ``target``
+    workgroups, each group the same whole number of consecutive tasks, no group empty; then as many
+    columns of env blocks as keep columns x groups within ``target`` -- at least one, never more
+    than there are env blocks (a column strides over the rest)."""
+    tasks = int(F) + 7
+    env_blocks = -(-int(n) // block)
+    wanted = min(max(-(-target // env_blocks), 1), tasks)
+    per_group = -(-tasks // wanted)
+    groups = -(-tasks // per_group)
+    columns = min(max(target // groups, 1), env_blocks)
+    return columns, groups, per_group
+
+
+def gl_float32_product(gamma, gae_lambda):
+    """The mutant's discount: gamma and lambda rounded to float32 FIRST, then multiplied in float32.
+    (0.99, 0.95) cannot tell it from float32(gamma * lambda in double); (0.9, 0.8) and (0.995, 0.97) do."""
+    return np.float32(gamma) * np.float32(gae_lambda)
 
 
 def slots(pos, count, T):

@@ -9,8 +9,18 @@
   4. returns / advantages against the float32 numpy loop of tests/rollout_ref.py, bit for bit:
      IEEE float32, one rounding per operation, the same order, nothing contracted, inputs on a
      1/1024 grid so that no intermediate comes near the denormal range -- equality is derived,
-     not a tolerance.
+     not a tolerance;
+  5. recording on every path of ``k_rollout_add`` that the launch policy can choose -- several rows
+     per workgroup, a second and third block of eight, a group that holds observation rows and
+     extra rows, the stride over envs -- each case reading its launch through
+     ``oc_rollout_add_plan`` and asserting the property it exists for BEFORE it launches; counter
+     words outside 0..T-1;
+  6. returns / advantages over more than one block of eight steps: a short second block, the ring's
+     wrap inside the first block, on a block boundary and in a later block, partly filled buffers,
+     counter words out of range, and (gamma, lambda) pairs at which float32(gamma * lambda in
+     double) is not the float32 product of the rounded factors.
 """
+import ctypes
 from types import SimpleNamespace
 
 import numpy as np
@@ -110,10 +120,14 @@ def test_fused_recording_converts_what_the_torch_path_converts(case):
 
 
 # ---- 2. inside a captured graph -------------------------------------------------------------------
-def test_fused_recording_inside_a_captured_graph():
+@pytest.mark.parametrize("n,F", [(130, 6), (3585, 29)], ids=["n130-F6", "two-rows-per-group"])
+def test_fused_recording_inside_a_captured_graph(n, F):
     from gym_comm_amd.vec_env import RolloutSink
-    per, replays, T, n, F = 4, 3, 5, 130, 6
+    per, replays, T = 4, 3, 5
     fused, plain = _pair(T, n, F, torch.int32)
+    if n > 256:                                # the ticket drawn by a few hundred workgroups under replay
+        gx, groups, pg = _plan(fused)
+        assert pg == 2 and _straddles(F, pg) and 200 <= gx * groups <= 512, (gx, groups, pg)
     gen = torch.Generator().manual_seed(21)
     d = _inputs(per * replays, n, F, torch.int32, gen)
     static = {key: t[:per].clone() for key, t in d.items()}
@@ -305,3 +319,180 @@ def test_gae_kernel_equals_closed_form_on_integers():
                                                   gamma=1.0, gae_lambda=1.0)
     ac, rc = rollout_ref.closed_form(r, v, es, lv, ld)
     assert (adv.cpu().numpy() == ac).all() and (ret.cpu().numpy() == rc).all()
+
+
+# ---- 5. recording, on every path the launch policy can choose -------------------------------------
+def _plan(sink):
+    """(gridDim.x, groups, per_group) of the launch ``oc_rollout_add`` makes for this sink."""
+    plan = (ctypes.c_int32 * 3)(-1, -1, -1)
+    assert sink._L.oc_rollout_add_plan(ctypes.byref(sink._buf), plan) == 0, sink._L.oc_rollout_last_error()
+    return tuple(plan)
+
+
+def _straddles(F, pg):
+    """some group holds the last observation row(s) AND the first extra row"""
+    return any(k * pg < F < (k + 1) * pg for k in range(F))
+
+
+# path -> (n, F, the property of the launch the case exists for); the smallest shapes found that have it
+PATHS = {
+    "two-rows-straddling": (3585, 29, lambda gx, groups, pg, n, F: pg == 2 and _straddles(F, pg)),
+    "three-to-seven-ragged": (2305, 120, lambda gx, groups, pg, n, F: 3 <= pg <= 7 and (F + 7) % pg != 0),
+    "second-block-partial": (2400, 497, lambda gx, groups, pg, n, F: 8 < pg < 16 and pg % 8 != 0 and
+                             _straddles(F, pg) and (F + 7) % pg != 0),
+    "three-blocks": (65536, 29, lambda gx, groups, pg, n, F: pg > 16 and groups == 2),
+    "grid-stride-uneven": (25601, 29, lambda gx, groups, pg, n, F: gx < (n + 255) // 256 < 2 * gx and n % 256 != 0),
+    "one-group-and-a-stride": (131073, 1, lambda gx, groups, pg, n, F: groups == 1 and gx < (n + 255) // 256),
+}
+PATH_CASES = [(path, torch.int32, True) for path in PATHS] + \
+             [(path, torch.int8, True) for path in ("second-block-partial", "three-blocks", "grid-stride-uneven")] + \
+             [("two-rows-straddling", torch.float32, True), ("three-to-seven-ragged", torch.int32, False)]
+PATTERN = 91                                     # what every buffer tensor holds before the first step
+
+
+def _fill_pattern(*sinks):
+    """A row that is never stored cannot pass as a zero, and a reward row that is not zeroed shows."""
+    for sink in sinks:
+        for f in FIELDS[:8]:
+            getattr(sink, f).fill_(PATTERN)
+
+
+@pytest.mark.parametrize("path,dt,value", PATH_CASES,
+                         ids=["%s-%s%s" % (p, str(d).split(".")[1], "" if v else "-no-value") for p, d, v in PATH_CASES])
+def test_fused_recording_on_every_path_of_the_add_kernel(path, dt, value):
+    n, F, has_property = PATHS[path]
+    K, T = 5, 2                                  # the ring wraps twice
+    fused, plain = _pair(T, n, F, dt)
+    plan = _plan(fused)
+    assert has_property(*plan, n, F), (path, plan)       # the case reaches the path it is named for
+    _fill_pattern(fused, plain)
+    d = _inputs(K + 1, n, F, dt, torch.Generator().manual_seed(n + F))
+    for k in range(K):
+        for sink in (fused, plain):
+            _add(sink, d, k, value=value)
+            if k == 1:                           # add, add again, then the reward
+                _add(sink, d, K, value=value)
+            sink.add_reward(d["reward"][k], d["done"][k])
+        _same(fused, plain, (path, k))
+    assert fused.steps() == K + 1 and int(fused.pos.item()) == (K + 1) % T
+    if not value:
+        assert bool((fused.values == PATTERN).all())
+
+
+@pytest.mark.parametrize("word", ["T+1", "-1", "2T"])
+def test_add_takes_a_position_outside_the_ring_modulo_T(word):
+    T, n, F = 3, 300, 2
+    bad = {"T+1": T + 1, "-1": -1, "2T": 2 * T}[word]
+    slot = bad % T                               # non-negative
+    assert slot == {"T+1": 1, "-1": 2, "2T": 0}[word]
+    fused, plain = _pair(T, n, F, torch.int32)
+    _fill_pattern(fused, plain)
+    d = _inputs(3, n, F, torch.int32, torch.Generator().manual_seed(5))
+    for sink in (fused, plain):                  # one ordinary step first: count is not 0
+        _add(sink, d, 0)
+        sink.add_reward(d["reward"][0], d["done"][0])
+    fused.pos.fill_(bad)
+    plain.pos.fill_(slot)                        # the torch sink only ever sees the reduced value
+    for sink in (fused, plain):
+        _add(sink, d, 1)
+    _same(fused, plain, "after the add")
+    assert (int(fused.last.item()), int(fused.pos.item()), fused.steps()) == (slot, (slot + 1) % T, 2)
+    for sink in (fused, plain):
+        sink.add_reward(d["reward"][1], d["done"][1])
+        _add(sink, d, 2)
+        sink.add_reward(d["reward"][2], d["done"][2])
+    _same(fused, plain, "after the next step")
+
+
+@pytest.mark.parametrize("word", ["T+1", "-1"])
+def test_add_reward_takes_a_last_outside_the_ring_modulo_T(word):
+    T, n, F = 3, 300, 2
+    bad = {"T+1": T + 1, "-1": -1}[word]
+    slot = bad % T
+    fused, plain = _pair(T, n, F, torch.int32)
+    _fill_pattern(fused, plain)
+    d = _inputs(2, n, F, torch.int32, torch.Generator().manual_seed(6))
+    for sink in (fused, plain):
+        _add(sink, d, 0)                         # slot 0; the reward below goes elsewhere, onto the pattern
+    fused.last.fill_(bad)
+    plain.last.fill_(slot)
+    for sink in (fused, plain):
+        sink.add_reward(d["reward"][1], d["done"][1])
+    assert int(fused.last.item()) == bad         # add_reward only reads the word
+    fused.last.fill_(slot)
+    _same(fused, plain, word)
+    want = d["reward"][1] + PATTERN
+    assert slot != 0 and torch.equal(_bits(fused.rewards[slot]), _bits(want))
+    assert torch.equal(fused.dones[slot], d["done"][1])
+
+
+# ---- 6. returns and advantages: blocks of eight, the ring and the counters ---------------------------
+def _ring_cases():
+    cases = []
+    for T in (9, 16, 17, 23):
+        for n in (1, 65):
+            cases.append((n, T, 0, T, "full"))
+            for pos in sorted({1, 7, 8, 9, T - 1}):
+                if pos < T:
+                    # the wrap inside the first block, on the block boundary, in a later block
+                    cases.append((n, T, pos, T + pos, "wrapped"))
+                    cases.append((n, T, pos, pos, "partial"))
+    cases.append((65, 17, 2, 3 * 17 + 2, "wrapped"))
+    T = 9                                        # counter words out of range: (pos, count) as the sink holds them
+    cases += [(65, T, T + 3, T, "pos=T+3"), (65, T, -1, T, "pos=-1"), (65, T, 0, 2 ** 40, "count=2^40"),
+              (65, T, 4, -5, "count=-5"), (65, T, 4, 0, "count=0")]
+    return [c + (0.99, 0.95) for c in cases]
+
+
+# two of the cases again, at pairs that tell float32(gamma * lambda in double) from the float32 product
+SHARP_PAIRS = ((0.9, 0.8), (0.995, 0.97))
+RING_CASES = _ring_cases() + [c + pair for pair in SHARP_PAIRS
+                              for c in ((65, 17, 9, 17 + 9, "wrapped"), (65, 23, 9, 9, "partial"))]
+
+
+@pytest.mark.parametrize("n,T,pos,count,state,gamma,lam", RING_CASES,
+                         ids=["n%d-T%d-pos%d-count%d-%s-g%s-l%s" % c for c in RING_CASES])
+def test_gae_kernel_over_blocks_ring_and_counters_bit_for_bit(n, T, pos, count, state, gamma, lam):
+    from gym_comm_amd.vec_env import RolloutSink
+    gen = torch.Generator().manual_seed(1000 * T + 10 * n + (pos % 7))
+    sink = RolloutSink(T, n, 1, obs_dtype=torch.float32, fused=True)
+    r, v = _grid(gen, T, n), _grid(gen, T, n).to(torch.float32)       # every slot holds numbers
+    es = (torch.rand((T, n), generator=gen) < 0.3).to(torch.float32)
+    lv = _grid(gen, n).to(torch.float32)
+    ld = torch.randint(0, 2, (n,), generator=gen).to(torch.float32)
+    sink.rewards.copy_(r)
+    sink.values.copy_(v)
+    sink.episode_starts.copy_(es)
+    sink.pos.fill_(pos)
+    sink.count.fill_(count)
+    sink.advantages.fill_(SENTINEL)
+    sink.returns.fill_(SENTINEL)
+    adv, ret = sink.compute_returns_and_advantage(lv.cuda(), ld.cuda(), gamma=gamma, gae_lambda=lam)
+    # the reference at the values the header reduces the words to
+    L = max(0, min(count, T))
+    order = np.array(rollout_ref.slots(pos % T, L, T), dtype=np.intp)
+    assert len(order) == L == {"full": T, "wrapped": T, "partial": pos, "pos=T+3": T, "pos=-1": T,
+                               "count=2^40": T, "count=-5": 0, "count=0": 0}[state]
+    data = (r.numpy()[order], v.numpy()[order], es.numpy()[order], lv.numpy(), ld.numpy())
+    ea, er = rollout_ref.gae(*data, gamma, lam, np.float32)
+    want_a = np.full((T, n), SENTINEL, np.float32)
+    want_r = np.full((T, n), SENTINEL, np.float32)
+    want_a[order], want_r[order] = ea, er                # slots that hold no step keep the sentinel
+    got_a, got_r = adv.cpu().numpy(), ret.cpu().numpy()
+    assert np.array_equal(got_a.view(np.int32), want_a.view(np.int32))
+    assert np.array_equal(got_r.view(np.int32), want_r.view(np.int32))
+    if state == "partial":                               # every slot from count upward
+        assert (got_a[count:] == SENTINEL).all() and (got_r[count:] == SENTINEL).all()
+        assert not (got_a[:count] == SENTINEL).any()
+    if L == 0:
+        assert (got_a == SENTINEL).all() and (got_r == SENTINEL).all()
+    assert int(sink.pos.item()) == pos and int(sink.count.item()) == count      # the counters are only read
+    if (gamma, lam) in SHARP_PAIRS:
+        # the pair tells the two products apart, and the planted mutant -- the product formed in
+        # float32 -- gives other advantages on this very data: the comparison above rejects it
+        mutant = rollout_ref.gl_float32_product(gamma, lam)
+        assert np.float32(gamma * lam) != mutant
+        ma, _ = rollout_ref.gae(*data, gamma, lam, np.float32, gl=mutant)
+        assert (ma.view(np.int32) != ea.view(np.int32)).any()
+    else:
+        assert np.float32(gamma * lam) == rollout_ref.gl_float32_product(gamma, lam)
