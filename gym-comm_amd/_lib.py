@@ -97,6 +97,7 @@ def _libs_table():
             "oc_obs_image": (cint, [vp, vp, i32, vp, vp, i64, vp]),
             "oc_multi_step": (cint, multi_step + [vp]),
             "oc_multi_step_waves": (i32, [i64, i32, i32]),
+            "oc_multi_step_lanes": (i32, [i64, i32, i32]),
             "oc_random_actions": (cint, [vp, vp, vp, i32, i64, vp]),
             "oc_timeline_begin": (cint, [vp, i64, i64]),
             "oc_multi_step_prepare": (cint, multi_step + [P(vp)]),

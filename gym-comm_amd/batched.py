@@ -176,6 +176,11 @@ class BatchedOvercooked:
         what ``OvercookedVecEnv`` launches), which splits four ways or not at all."""
         return int(self._L.oc_multi_step_waves(self.n, self.waves_per_64, 1 if general else 0))
 
+    def launch_lanes(self, general=False):
+        """Lanes per env of that launch (include/oc_hip.h: oc_multi_step_lanes): 1, or 2 where
+        the library lane-splits the plain step's four-way split at a small batch."""
+        return int(self._L.oc_multi_step_lanes(self.n, self.waves_per_64, 1 if general else 0))
+
     # -- helpers ---------------------------------------------------------------
     def _on_device(self):
         """Kernels must be launched with this env's device current."""

@@ -126,11 +126,12 @@ unsigned long long *timeline_next(int64_t waves, int64_t &stride) {
 //     wt          1 = write-through (sc1) stores, 0 = write-back                      [write_through]
 //     lds         1 = the lane-indexed tables staged in LDS (one wave per 64 envs)    [tables_in_lds]
 //     block       threads per workgroup of an unsplit launch: 64, 128 or 256          [block_size_for]
+//     lanes       lanes per env of the fused step's plain four-way split: 1 or 2      [lanes_for]
 // Read at EVERY call (a getenv and a string compare), so one process can run several policies --
 // tests/test_hip_parity.py::test_forced_launch_policies does.  Results never depend on it.
 // (Round 2 had six variables, three of them latched at first use; they are gone.)
 struct LaunchPolicy {
-  int split = 0, step_split = 0, wt = -1, lds = -1, block = 0;
+  int split = 0, step_split = 0, wt = -1, lds = -1, block = 0, lanes = 0;
 };
 LaunchPolicy launch_policy() {
   static thread_local char seen[128] = "\x01";
@@ -150,6 +151,7 @@ LaunchPolicy launch_policy() {
       else if (!strcmp(key, "wt") && (val == 0 || val == 1)) p.wt = val;
       else if (!strcmp(key, "lds") && (val == 0 || val == 1)) p.lds = val;
       else if (!strcmp(key, "block") && (val == 64 || val == 128 || val == 256)) p.block = val;
+      else if (!strcmp(key, "lanes") && (val == 1 || val == 2)) p.lanes = val;
       q += used;
     }
     while (*q && *q != ',') q++;
@@ -176,8 +178,8 @@ bool fits_buffer(int64_t n, int64_t rows, int elem) { return n * rows * elem < (
 struct Shape {
   int envs, threads;   // per workgroup
 };
-Shape shape_for(int64_t n, int sp) {
-  if (sp > 1) return {64, 64 * sp};
+Shape shape_for(int64_t n, int sp, int ln = 1) {
+  if (sp > 1) return {64 / ln, 64 * sp};   // (lane-split: ln lanes per env, 64 / ln envs per workgroup)
   const int bs = block_size_for(n);
   return {bs, bs};
 }
@@ -208,6 +210,21 @@ int split_for(int64_t n, int hint) {
   if (forced) return forced;
   if (hint == 1 || hint == 2 || hint == 4) return hint;
   return n <= 32768 ? 4 : 1;
+}
+
+// Lanes per env of the plain four-way split (k_multi_step<..., LN>, see LaneParts): two while the
+// launch's 8 * n / 64 waves still find a SIMD of their own (1 024 on the chip), so that the extra
+// waves run on CUs that would otherwise idle.  us per step, one / two / four lanes per env (MI355X,
+// profiles/lane_split_ab.txt, medians of five alternating runs):
+//   tomato-2  4 096 2.705 / 2.630 / 2.715   8 192 2.756 / 2.703 / 3.439   16 384 2.953 / 3.443 / 4.847
+//             32 768 3.750 / 4.915 / 7.598   salad-2  32 768 3.958 / 4.967 / 7.715
+// (four lanes per env never won and are not built).  OC_LAUNCH=lanes=... overrides; a library or
+// variant without the kernel runs one lane per env (select_multi).
+constexpr int64_t LANES2_MAX_N = 8192;
+int lanes_for(int64_t n) {
+  const int forced = launch_policy().lanes;
+  if (forced) return forced;
+  return n <= LANES2_MAX_N ? 2 : 1;
 }
 
 // The same for the base step (k_step<..., SP = 2>: state wave + shaping wave): two up to 16 384
@@ -306,9 +323,11 @@ struct MultiVariant {
   bool wt;
   int xo, sp;
   bool pol;
+  int ln = 1;   // lanes per env
 };
 constexpr bool held(MultiVariant v) {
   if (v.xo == 1 && !SPEC) return false;
+  if (v.ln != 1 && !(SPEC && v.ln == 2 && v.xo == 0 && v.sp == 4 && !v.pol && v.wt && !v.lds)) return false;
   if (v.lds) return v.ot == 0 && !v.wt && v.sp == 1 && !v.pol;   // (the split launches read global memory)
   if (v.pol) return SPEC && v.wt && v.xo == 1 && v.sp != 2;
   if (v.sp == 4) return v.wt && (SPEC || v.xo == 0);
@@ -324,6 +343,8 @@ MultiVariant select_multi(int ot, bool general, bool std_cfg, bool pol, int hint
   if (general) v.xo = std_cfg && held(x1) ? 1 : 2;
   if (v.wt && !in_lds) v.sp = split_for(n, hint);   // the policy's wish ...
   if (!held(v)) v.sp = 1;                           // ... and what this library has kernels for
+  v.ln = lanes_for(n);
+  if (!held(v)) v.ln = 1;
   if (in_lds && ot == 0) v.lds = true, v.wt = false;   // (int8 / float32 rows: the global-table variant)
   return v;
 }
@@ -577,21 +598,21 @@ int oc_multi_step(const oc_level_t *lv, int32_t *state, int32_t *comm, const int
     return fail(OC_E_BADARG, "oc_multi_step: opts.policy needs write-through stores and tables in global memory");
   MultiVariant v = select_multi(ot, opts_used || !std_cfg, std_cfg, o.policy != nullptr, o.waves_per_64, n);
   v.M = lv->hdr.M, v.dup = lv->hdr.has_dup != 0;
-  const Shape shape = shape_for(n, v.sp);
+  const Shape shape = shape_for(n, v.sp, v.ln);
   // the hot scalars lead (see k_multi_step): block_ = envs per workgroup | action sources in use << 16
   const int32_t src = (o.ego_pairs ? 1 : 0) | (o.alt_pairs ? 2 : 0) | (o.alt_rng ? 4 : 0) | (o.pairs_int64 ? 8 : 0);
   const int32_t block_ = shape.envs | (src << 16);
   const void *const alt_src = o.alt_rng ? (const void *)o.alt_rng : (const void *)o.alt_pairs;
-  return no_kernel(lift([&](auto M, auto D, auto LDS, auto OT, auto WT, auto XO, auto SP, auto POL) {
-                          if constexpr (held(MultiVariant{M, D, LDS, OT, WT, XO, SP, POL}))
-                            return launch(k_multi_step<M, LDS, OT, WT, D, XO, SP, POL>, shape, n,
+  return no_kernel(lift([&](auto M, auto D, auto LDS, auto OT, auto WT, auto XO, auto SP, auto POL, auto LN) {
+                          if constexpr (held(MultiVariant{M, D, LDS, OT, WT, XO, SP, POL, LN}))
+                            return launch(k_multi_step<M, LDS, OT, WT, D, XO, SP, POL, LN>, shape, n,
                                           v.lds ? (size_t)lv->n16 * 16 : 0, stream, a.state, a.actions, a.comm, a.metrics,
                                           (int32_t)a.n, block_, (const void *)o.ego_pairs, alt_src, a);
                           else
                             return not_held();
                         },
                         Items{v.M}, Dup{v.dup}, Bool{v.lds}, ObsType{v.ot}, Bool{v.wt}, Among<int, 0, 1, 2>{v.xo},
-                        Among<int, 1, 2, 4>{v.sp}, Bool{v.pol}),
+                        Among<int, 1, 2, 4>{v.sp}, Bool{v.pol}, Among<int, 1, 2>{v.ln}),
                    "oc_multi_step: unsupported number of items");
 }
 
@@ -650,6 +671,10 @@ int oc_timeline_begin(uint64_t *records, int64_t count, int64_t stride) {
 
 int32_t oc_multi_step_waves(int64_t n, int32_t hint, int32_t general_variant) {
   return select_multi(0, general_variant != 0, false, false, hint, n).sp;
+}
+
+int32_t oc_multi_step_lanes(int64_t n, int32_t hint, int32_t general_variant) {
+  return select_multi(0, general_variant != 0, false, false, hint, n).ln;
 }
 
 int oc_random_actions(uint32_t *rng, int32_t *move_row, int32_t *comm_row, int32_t num_comm, int64_t n,

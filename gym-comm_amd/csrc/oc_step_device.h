@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/oc_hip.h"
 #include "oc_level_host.h"
 #include "oc_policy_device.h"
@@ -51,7 +53,7 @@ namespace {
 #define OC_TL_BEGIN()                                                            \
   const unsigned long long oc_tl0_ = __builtin_amdgcn_s_memrealtime();           \
   const unsigned long long oc_tc0_ = __builtin_amdgcn_s_memtime()
-#define OC_TL_END(ptr_, stride_)                                                                 \
+#define OC_TL_END(ptr_, stride_, ln_)                                                            \
   do {                                                                                           \
     __builtin_amdgcn_sched_barrier(0);                                                           \
     const unsigned long long oc_tl1_ = __builtin_amdgcn_s_memrealtime();                         \
@@ -62,11 +64,13 @@ namespace {
     }                                                                                            \
     const unsigned long long oc_tc2_ = __builtin_amdgcn_s_memtime();                             \
     unsigned long long *tl_ = (ptr_);                                                            \
-    if (tl_ != nullptr && (threadIdx.x & 63) == 0) {                                             \
+    /* (a lane-split launch, ln_ workgroups per 64 envs: every ln_-th workgroup writes, so the   \
+       record keeps its 4 * ceil(n / 64) waves -- a SAMPLE of the launch's waves) */             \
+    if (tl_ != nullptr && (threadIdx.x & 63) == 0 && blockIdx.x % (ln_) == 0) {                  \
       /* ONE 16-byte write-through store per wave: {start (64 bits), issue-end - start | (drain-end  \
          - start) << 16, shader cycles}; spans are < 65 536 ticks (655 us) */                     \
       typedef int v4i_ __attribute__((ext_vector_type(4)));                                      \
-      const int64_t w_ = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);           \
+      const int64_t w_ = (int64_t)(blockIdx.x / (ln_)) * (blockDim.x >> 6) + (threadIdx.x >> 6); \
       const __amdgpu_buffer_rsrc_t r_ = __builtin_amdgcn_make_buffer_rsrc(tl_, 0, 0x7FFFFFFF, 0x00020000); \
       const unsigned d1_ = (unsigned)min((unsigned long long)0xFFFF, oc_tl1_ - oc_tl0_);         \
       const unsigned d2_ = (unsigned)min((unsigned long long)0xFFFF, oc_tl2_ - oc_tl0_);         \
@@ -80,7 +84,7 @@ namespace {
   } while (0)
 #else
 #define OC_TL_BEGIN() do { } while (0)
-#define OC_TL_END(ptr_, stride_) do { } while (0)
+#define OC_TL_END(ptr_, stride_, ln_) do { } while (0)
 #endif
 
 // The kernels read the level through ACCESSORS (L.W(), L.goal_tset(g), ...), generated from the
@@ -380,6 +384,14 @@ struct RowsPreT : RowsT<AUX> {   // (N == 0: no table, a plain RowsT)
   }
   __device__ __forceinline__ void st8(int row, int v) const {
     __builtin_amdgcn_raw_buffer_store_b8((char)v, this->rsrc, this->voff, off(row), AUX);
+  }
+  // the same with the lane's byte offset given by the caller: a lane-split launch (LaneParts) adds
+  // the distance to its part's row to it, so ONE store writes a different row in every part
+  __device__ __forceinline__ void st_v(int row, int vo, int v) const {
+    __builtin_amdgcn_raw_buffer_store_b32(v, this->rsrc, vo, off(row), AUX);
+  }
+  __device__ __forceinline__ void st8_v(int row, int vo, int v) const {
+    __builtin_amdgcn_raw_buffer_store_b8((char)v, this->rsrc, vo, off(row), AUX);
   }
 };
 // RowsT that also leaves every stored value, as a float, in an LDS image [row - rowbase][64 lanes]:
@@ -1162,6 +1174,158 @@ __device__ __forceinline__ void env_obs(const Hdr &L, const RunCfg &R, const Obs
 #undef OUT
 }
 
+#ifdef OC_SPECIALIZED
+// LANE-SPLIT launch (k_multi_step<..., LN = 2>; four lanes per env were built, measured slower at
+// every batch size and taken out again): an env has LN lanes of every wave -- lane l of
+// the wave serves env (l mod 64/LN) of the workgroup as PART l / (64/LN) -- and the parts of an env
+// produce DIFFERENT observation rows with the SAME instructions: the row of a part lies a constant
+// number of rows behind part 0's, so the distance is added once, per lane, to the byte offset the
+// store takes anyway, and one row store writes LN rows.  What a part needs of the launch alone is
+// formed here, by the observation waves, under the wait for the state:
+//   voA  channel rows (ddx / ddy / st / hid) and the agent locations: part p takes the 4 / LN
+//        channels (location words) from p * 4 / LN on, i.e. rows 4 / LN apart
+//   vo1  rows paired at distance 1 (subtask bits two by two, holding + the zero row)
+//   voC  the comm one-hots, comm1[c] C rows behind comm0[c]
+//   hi   the part as a P word (0 / -1), shp[k] the bit of `completed` that subtask row 2 k (part 1:
+//        2 k + 1) shows
+template <int LN>
+struct LaneParts {
+  static_assert(LN == 2, "lanes per env");
+  static constexpr int NPAIR = (int)OC_SPEC_HDR.S / 2;
+  int voA, vo1, voC;
+  P hi;
+  int shp[NPAIR > 0 ? NPAIR : 1];
+  int sh_odd;   // (uniform) the bit an odd last subtask row shows: stored by every part
+  template <int AUX>
+  __device__ __forceinline__ LaneParts(const RowsT<AUX> &ob, const ObsSlots &slots, int C) {
+    const int tid = (int)threadIdx.x;
+    hi = p_bit(tid, 5);
+    voA = ob.voff + (hi & ((4 / LN) * ob.rowbytes));
+    vo1 = ob.voff + (hi & ob.rowbytes);
+    voC = ob.voff + (hi & (C * ob.rowbytes));
+    asm volatile("" : "+v"(voA), "+v"(vo1), "+v"(voC), "+v"(hi));   // formed HERE, like RowsPreT's offsets
+#pragma unroll
+    for (int k = 0; k < NPAIR; k++) {
+      shp[k] = sel(hi, slots.sh[2 * k + 1], slots.sh[2 * k]);
+      asm volatile("" : "+v"(shp[k]));
+    }
+    sh_odd = (OC_SPEC_HDR.S & 1) ? slots.sh[OBS_NSLOT - 1] : 0;
+  }
+  // the value of this lane's part among one per part
+  __device__ __forceinline__ int pick(const int (&v)[LN]) const { return sel(hi, v[1], v[0]); }
+};
+
+struct NoParts {   // (what a wave that is not a lane-split observation wave holds instead)
+  template <typename... T>
+  __device__ __forceinline__ NoParts(const T &...) {}
+};
+
+// env_obs for one part of a lane-split launch: the plain variant's configuration (nobody BLIND),
+// the same rows with the same values -- each stored by the part LaneParts names, the rest (an odd
+// subtask row, the comm rows of more than four channels, the timestep by the caller) by every
+// part alike: the same value to the same address.
+template <int A, int M, bool DUP, int OT, int LN, typename OutRows>
+__device__ __forceinline__ void env_obs_lanes(const Hdr &L, const LaneParts<LN> &lp, const Env<A, M, DUP> &e,
+                                              int viewer, int radius, int C, int comm0, int comm1,
+                                              const OutRows &out, int row0) {
+  constexpr int CPP = 4 / LN;   // channels (location words) per part
+  constexpr int S = (int)OC_SPEC_HDR.S;
+  const int vp = viewer == 0 ? e.ap[0] : e.ap[1];
+  const int vhp = viewer == 0 ? e.ahp[0] : e.ahp[1];
+  const int vx = px(vp), vy = py(vp);
+  const int loc4[4] = {px(e.ap[0]), py(e.ap[0]), px(e.ap[1]), py(e.ap[1])};
+  int ddx[CPP], ddy[CPP], st[CPP], hid[CPP], loc[CPP];
+#pragma unroll
+  for (int j = 0; j < CPP; j++) {
+    // channel q * CPP + j in part q: its winning item word (see env_obs), selected BEFORE the
+    // arithmetic all parts share
+    int bwq[LN], anyq[LN], chopq[LN], locq[LN];
+#pragma unroll
+    for (int q = 0; q < LN; q++) {
+      const int ch = q * CPP + j;
+      int bw = 0;
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < M; i++)
+        if (item_type(L, i) == ch) {  // uniform
+          bw = (!any || (e.iw[i] & IW_SEQ) > (bw & IW_SEQ)) ? e.iw[i] : bw;
+          any = true;
+        }
+      bwq[q] = bw;
+      anyq[q] = any ? -1 : 0;
+      chopq[q] = (any && ch != OC_PLATE) ? 1 : 0;
+      locq[q] = loc4[ch];
+    }
+    const int bw = lp.pick(bwq);
+    const P any = lp.pick(anyq);
+    const int bx = sel(any, px(ipos(bw)), vx), by = sel(any, py(ipos(bw)), vy);   // an absent type keeps delta (0,0)
+    const bool within = (int)sad_u32(bx, vx, sad_u32(by, vy, 0u)) <= radius;
+    hid[j] = within ? 0 : 1;
+    ddx[j] = within ? 0 : bx - vx;
+    ddy[j] = within ? 0 : by - vy;
+    st[j] = ichop(bw) & lp.pick(chopq);
+    loc[j] = lp.pick(locq);
+  }
+#define OUTV(r_, vo_, v_)                                                               \
+  do {                                                                                  \
+    if (OT == 1) out.st8_v((r_), (vo_), (v_));                                          \
+    else if (OT == 2) out.st_v((r_), (vo_), __builtin_bit_cast(int, (float)(v_)));      \
+    else out.st_v((r_), (vo_), (v_));                                                   \
+  } while (0)
+  int row = row0;
+#pragma unroll
+  for (int j = 0; j < CPP; j++) OUTV(row + j, lp.voA, ddx[j]);
+#pragma unroll
+  for (int j = 0; j < CPP; j++) OUTV(row + 4 + j, lp.voA, ddy[j]);
+#pragma unroll
+  for (int j = 0; j < CPP; j++) OUTV(row + 8 + j, lp.voA, st[j]);
+#pragma unroll
+  for (int j = 0; j < CPP; j++) OUTV(row + 12 + j, lp.voA, hid[j]);
+  row += 16;
+#pragma unroll
+  for (int k = 0; k < S / 2; k++) OUTV(row + 2 * k, lp.vo1, (e.completed >> lp.shp[k]) & 1);
+  if constexpr ((S & 1) != 0) OUTV(row + S - 1, out.voff, (e.completed >> lp.sh_odd) & 1);
+  row += S;
+#pragma unroll
+  for (int j = 0; j < CPP; j++) OUTV(row + j, lp.voA, loc[j]);
+  row += 4;
+  OUTV(row, lp.vo1, p_nz(vhp) & ~lp.hi & 1);   // holding | the zero row behind it
+  row += 2;
+  const int commv = sel(lp.hi, comm1, comm0);
+#define COMM_ROWS(CC_)                                                                              \
+  do {                                                                                              \
+    _Pragma("unroll") for (int c = 0; c < (CC_); c++) OUTV(row + c, lp.voC, commv == c ? 1 : 0);   \
+    asm volatile("");                                                                               \
+  } while (0)
+  if (C == 2) {
+    COMM_ROWS(2);
+  } else {
+    int Cx = C;
+    asm("" : "+s"(Cx));
+    switch (Cx) {
+      case 1: COMM_ROWS(1); break;
+      case 3: COMM_ROWS(3); break;
+      case 4: COMM_ROWS(4); break;
+      default: {   // the loop stays unsplit
+        int so = out.soff(row);
+        for (int c = 0; c < C; c++, row++, so += out.rowbytes) {
+          if (OT == 1) out.st8_at(so, row, comm0 == c ? 1 : 0);
+          else if (OT == 2) out.st_at(so, row, __builtin_bit_cast(int, (float)(comm0 == c ? 1 : 0)));
+          else out.st_at(so, row, comm0 == c ? 1 : 0);
+        }
+        for (int c = 0; c < C; c++, row++, so += out.rowbytes) {
+          if (OT == 1) out.st8_at(so, row, comm1 == c ? 1 : 0);
+          else if (OT == 2) out.st_at(so, row, __builtin_bit_cast(int, (float)(comm1 == c ? 1 : 0)));
+          else out.st_at(so, row, comm1 == c ? 1 : 0);
+        }
+      }
+    }
+  }
+#undef COMM_ROWS
+#undef OUTV
+}
+#endif
+
 // Sum of a per-lane integer over the 64 lanes of the wave, left in lane 63: an inclusive scan
 // inside each row of 16 lanes (row_shr 1/2/4/8, zero fill), then row 0 -> 1, 2 -> 3
 // (row_bcast:15) and rows 0-1 -> 2-3 (row_bcast:31).  Six DPP adds, no LDS, no SALU loop.
@@ -1449,7 +1613,7 @@ __global__ void __launch_bounds__(256) k_step(int32_t *const state_, const int32
     else
       step_body<A, M, LDS, WT, DUP, PLAY, 2, true>(state_, actions_, metrics_, n_, launch_, T_, tables_, inv_max_path_, p);
   }
-  OC_TL_END(p.timeline, p.timeline_stride);
+  OC_TL_END(p.timeline, p.timeline_stride, 1);
 }
 
 struct ObsArgs {
@@ -1709,7 +1873,11 @@ __device__ __forceinline__ float *pol_lds_ts() {
 // one wave x 32 envs; a split workgroup gives each of its four waves one (viewer, half) pass
 // behind a second barrier ("every observation row of these 64 envs is written"), a lone wave
 // runs all four.
-template <int M, bool LDS, int OT, bool WT, bool DUP, int XO, int DUTY, bool SPLIT, bool POL = false>
+// LN (lane-split launch, see LaneParts): lanes per env, 1 or 2.  A workgroup of LN > 1 is still
+// four duty waves and one barrier but covers 64 / LN envs; every lane runs its env's step up to
+// done/reward (the parts of an env compute identical values), an observation wave's parts then
+// store different rows, and the state and shaping waves work in part 0 alone.
+template <int M, bool LDS, int OT, bool WT, bool DUP, int XO, int DUTY, bool SPLIT, bool POL = false, int LN = 1>
 __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int32_t *const actions_,
                                                 int32_t *const comm_, int64_t *const metrics_,
                                                 const int32_t n_, const int32_t block_, const void *const ego_src_,
@@ -1724,9 +1892,13 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
 #endif
   OC_HDR_LOAD(p);
   // n < 2^31 / (4 * rows): fits_buffer().  Split: one workgroup = SP waves over the same 64 envs.
-  const int i = SPLIT ? (int)blockIdx.x * 64 + (int)(threadIdx.x & 63)
+  static_assert(LN == 1 || (SPLIT && XO == 0 && !POL && !LDS && DUTY != DUTY_ALL), "lane-split: the plain four-way split only");
+  constexpr int EPW = 64 / LN;   // envs per split workgroup
+  const int i = SPLIT ? (int)blockIdx.x * EPW + (int)(threadIdx.x & (EPW - 1))
                       : (int)blockIdx.x * (block_ & 0xFFFF) + (int)threadIdx.x;
-  const bool valid = i < (int)n_;
+  // (lane-split: only the observation waves have work for the parts behind part 0)
+  constexpr bool PART0_ONLY = LN > 1 && (DUTY & (DUTY_OBS0 | DUTY_OBS1)) == 0;
+  const bool valid = PART0_ONLY ? (i < (int)n_ && (int)(threadIdx.x & 63) < EPW) : i < (int)n_;
   const bool ego_from_pairs = XO != 0 && ((block_ >> 16) & 1), alt_from_pairs = XO != 0 && ((block_ >> 17) & 1),
              alt_from_rng = XO != 0 && ((block_ >> 18) & 1), pairs64 = XO != 0 && ((block_ >> 19) & 1);
 #ifdef OC_STAMPS
@@ -1862,6 +2034,11 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     const ObsSlots slots(p.R, NPRE != 0);
     const RowsPreT<WT ? AUX_WT : 0, NPRE> obp(ob, DUTY == DUTY_OBS1 ? F : 0);
     if constexpr (NPRE != 0) asm volatile("" ::"s"(ob.rsrc));   // (the descriptor's words as well)
+#ifdef OC_SPECIALIZED
+    // (lane-split: what this lane's part adds to the offsets and selects, formed here as well)
+    using Parts = std::conditional_t<(LN > 1 && OBS_ONLY), LaneParts<(LN > 1 ? LN : 2)>, NoParts>;
+    [[maybe_unused]] const Parts parts(ob, slots, C);
+#endif
     const Out tso(p.timestep, p.n, 1, i, 8);
     if constexpr (NPRE != 0 && DUTY == DUTY_OBS0) asm volatile("" ::"s"(tso.rsrc), "v"(tso.voff));
     // split: nothing that is updated in place -- state rows, the words of the random streams, the
@@ -2009,10 +2186,18 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
       }
     } else {
       // (obp: the rows with this wave's offsets pre-formed, or plain rows where none were)
-      if constexpr ((DUTY & DUTY_OBS0) != 0)
-        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obp, 0);
-      if constexpr ((DUTY & DUTY_OBS1) != 0)
-        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obp, F);
+#ifdef OC_SPECIALIZED
+      if constexpr (LN > 1) {
+        if constexpr (DUTY == DUTY_OBS0) env_obs_lanes<A, M, DUP, OT, LN>(L, parts, e, 0, p.cfg.obs.fow_radius, C, c0, c1, obp, 0);
+        if constexpr (DUTY == DUTY_OBS1) env_obs_lanes<A, M, DUP, OT, LN>(L, parts, e, 1, p.cfg.obs.fow_radius, C, c0, c1, obp, F);
+      } else
+#endif
+      {
+        if constexpr ((DUTY & DUTY_OBS0) != 0)
+          env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obp, 0);
+        if constexpr ((DUTY & DUTY_OBS1) != 0)
+          env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obp, F);
+      }
       if constexpr ((DUTY & DUTY_OBS0) != 0) tso.st_f64(0, timestep_of(e.t, p.R));
     }
     OC_STAMP(5);   // observation stores issued
@@ -2083,7 +2268,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
 // not on a pointer that a scalar load has yet to deliver; ego_src_ = opts.ego_pairs, alt_src_ =
 // opts.alt_rng or opts.alt_pairs: preloaded as well (n_ is 32 bits wide so that the lot fits the
 // 14 preloadable dwords), so the general variant issues its action loads with the state loads)
-template <int M, bool LDS, int OT, bool WT, bool DUP, int XO, int SP, bool POL = false>
+template <int M, bool LDS, int OT, bool WT, bool DUP, int XO, int SP, bool POL = false, int LN = 1>
 __global__ void __launch_bounds__(256) k_multi_step(int32_t *const state_, const int32_t *const actions_,
                                                     int32_t *const comm_, int64_t *const metrics_,
                                                     const int32_t n_, const int32_t block_,
@@ -2092,6 +2277,7 @@ __global__ void __launch_bounds__(256) k_multi_step(int32_t *const state_, const
   static_assert(SP == 1 || SP == 2 || SP == 4, "waves per 64 envs");
   static_assert(SP != 2 || !POL, "the fused policies need the four-wave split");
   static_assert(SP == 1 || !LDS, "the split launch reads the tables from global memory");
+  static_assert(LN == 1 || (SP == 4 && XO == 0 && !POL), "lanes per env: the plain four-way split only");
   OC_TL_BEGIN();
 #ifdef OC_SPECIALIZED
   const MultiArgs &pk = p;
@@ -2108,7 +2294,7 @@ __global__ void __launch_bounds__(256) k_multi_step(int32_t *const state_, const
   [[maybe_unused]] const MultiArgs &pk = *reinterpret_cast<const MultiArgs *>(
       reinterpret_cast<const char *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(KernArgs, p));
 #endif
-#define OC_BODY(duty) multi_step_body<M, LDS, OT, WT, DUP, XO, (duty), true, POL>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, pk)
+#define OC_BODY(duty) multi_step_body<M, LDS, OT, WT, DUP, XO, (duty), true, POL, LN>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, pk)
   if constexpr (SP == 1) {
     multi_step_body<M, LDS, OT, WT, DUP, XO, DUTY_ALL, false, POL>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, p);
   } else {
@@ -2129,7 +2315,7 @@ __global__ void __launch_bounds__(256) k_multi_step(int32_t *const state_, const
     }
   }
 #undef OC_BODY
-  OC_TL_END(p.timeline, p.timeline_stride);
+  OC_TL_END(p.timeline, p.timeline_stride, LN);
 }
 
 }  // namespace

@@ -278,6 +278,12 @@ OC_API int oc_call_destroy(oc_call_t *call);
  * (a measurement knob, csrc/oc_kernels.hip: launch_policy) overrides the policy, never the
  * results.  Host only; for reports and tests. */
 OC_API int32_t oc_multi_step_waves(int64_t n, int32_t hint, int32_t general_variant);
+/* Lanes per env of that launch: 1, or 2 -- a lane-split launch of the plain step's four-way
+ * split in a specialised library, where small batches leave most of the chip idle: a workgroup
+ * then covers 64 / lanes envs and the lanes of an env store different observation rows with the
+ * same instructions (csrc/oc_step_device.h: LaneParts).  oc_multi_step_waves keeps reporting the
+ * duty split.  OC_LAUNCH=lanes=... overrides the policy, never the results.  Host only. */
+OC_API int32_t oc_multi_step_lanes(int64_t n, int32_t hint, int32_t general_variant);
 
 /* Measurement hook of the TIMELINE build flavour (the same source compiled with -DOC_TIMELINE=1;
  * gym-comm_amd/specialize.py, variant="timeline"; every other build returns OC_E_BADARG).  In such a

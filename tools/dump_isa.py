@@ -44,14 +44,17 @@ def classify(op):
     return "OTHER"
 
 
-def kernel_digest(body):
+def kernel_digest(body, symbol=""):
     """sha256 over a kernel's labels + instructions and its .amdhsa_kernel descriptor block,
     comments and every other directive stripped (branch labels stay, without the index of the
-    function in the module: .LBB<fn>_<n>, which only says in which order kernels were emitted)"""
+    function in the module: .LBB<fn>_<n>, which only says in which order kernels were emitted; the
+    kernel's own mangled name is replaced, so a kernel keeps its digest when its template gains an axis)"""
     lines = []
     code, _, rest = body.partition(".amdhsa_kernel")
     for ln in code.splitlines():
         ln = re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";")[0].strip())
+        if symbol:          # (the kernel's own label: a new template axis renames it, the code is the same)
+            ln = ln.replace(symbol, "<kernel>")
         if ln and (ln.startswith(".LBB_") or not ln.startswith(".")):
             lines.append(ln)
     for ln in rest.split(".end_amdhsa_kernel")[0].splitlines()[1:]:
@@ -94,7 +97,7 @@ def main():
             if ".amdhsa_kernel" not in parts[k + 1]:
                 continue
             dem = subprocess.run(["c++filt", parts[k]], capture_output=True, text=True).stdout.strip()
-            rows.append("%s %5d  %s" % (*kernel_digest(parts[k + 1]), dem))
+            rows.append("%s %5d  %s" % (*kernel_digest(parts[k + 1], parts[k]), dem))
         print("\n".join(sorted(rows, key=lambda r: r.split("  ", 1)[1])))
         print("kernels:", len(rows))
         return

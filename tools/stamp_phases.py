@@ -27,7 +27,8 @@ def main():
                             waves_per_64=int(sys.argv[2]) if len(sys.argv) > 2 else 0,
                             episode_stats=len(sys.argv) > 3 and sys.argv[3] in ("stats", "rng"))   # rows + statistics: the options variant
     sp = env.launch_waves(general=len(sys.argv) > 3)    # waves per 64 envs (4 = split launch): the kernel writes one record per wave
-    waves = (n + 63) // 64 * sp
+    ln = env.launch_lanes(general=len(sys.argv) > 3)    # lanes per env: a workgroup covers 64 / ln envs
+    waves = (n * ln + 63) // 64 * sp
     dbg = torch.zeros((waves, 16), dtype=torch.int64, device="cuda")
     env.reward = dbg.view(torch.int32)          # the stamps build writes its stamps through `sparse`
     gen = torch.Generator(device="cuda").manual_seed(1)
@@ -48,7 +49,8 @@ def main():
         if k >= 100:
             rows.append(dbg.cpu().numpy().copy())
     t = np.stack(rows).astype(np.int64)          # [steps][waves][16]
-    print("n = %d, %d waves (%d per 64 envs); median shader cycles per phase (one wave):" % (n, waves, sp))
+    print("n = %d, %d waves (%d per workgroup, %d lane(s) per env); median shader cycles per phase (one wave):"
+          % (n, waves, sp, ln))
     for role in range(sp):
         tr = t[:, role::sp, :9]
         taken = [k for k in range(9) if (tr[:, :, k] != 0).all()]    # a wave only stamps the phases of its duties
