@@ -74,6 +74,10 @@ typedef struct {
   /* random-* levels: start cell (x | y<<4) of every item for the NEXT reset, -1 = the
    * blob's default (overcooked_environment.py:157-173 draws them with random.choice) */
   int next_place[OC_MAX_ITEMS];
+  /* what the last wrapper step (oc_oracle_batch_multi_step) saw BEFORE a possible auto-reset: the
+   * sparse reward, `successful`, the number of completed subtasks if the episode ended (else 0),
+   * and whether the step raised an error flag -- the terms of the library's metrics counters */
+  int last[4];
 } Env;
 
 static const int NAV_DX[5] = {0, 0, -1, 1, 0};
@@ -906,10 +910,16 @@ OC_EXPORT void oc_oracle_batch_multi_step(void **envs, int64_t n0, int64_t n1, i
     if ((can_move_mask & 2) && alt_mv >= 0 && alt_mv <= 3) act[1 - ego_slot] = alt_mv;
     int32_t r, d;
     double sh[2];
+    const int err_before = e->err;
     if (bad) e->err |= OC_ERR_ACTION;
     oc_oracle_step(e, act, &r, &d, sh);
     reward[i] = (double)r - sh[0] - sh[1];                             /* :282 */
     done[i] = d;
+    e->last[0] = r;
+    e->last[1] = e->successful;
+    e->last[2] = 0;
+    for (int s = 0; d && s < e->S; s++) e->last[2] += e->completed[s] != 0;
+    e->last[3] = e->err != err_before;
     if (auto_reset && d) env_reset(e);
     int32_t tmp[22 + OC_MAX_SUBTASKS + 2 * 128]; /* C <= 128 */
     int32_t cm[2] = {comm[i], comm[n_stride + i]};
@@ -933,6 +943,12 @@ OC_EXPORT void oc_oracle_batch_snapshot(void **envs, int64_t n, int32_t *items, 
                        completed + i * e->S, goalcnt + i * e->S);
     err[i] = e->err;
   }
+}
+
+/* out [4][n]: Env.last of envs [0, n) (see there) */
+OC_EXPORT void oc_oracle_batch_last_step(void **envs, int64_t n, int32_t *out) {
+  for (int64_t i = 0; i < n; i++)
+    for (int k = 0; k < 4; k++) out[k * n + i] = ((const Env *)envs[i])->last[k];
 }
 
 OC_EXPORT void oc_oracle_batch_reset(void **envs, int64_t n, const int32_t *mask) {

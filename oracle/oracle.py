@@ -74,6 +74,7 @@ def lib():
             [ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int64] * 4 + [ctypes.c_int, _I32P, _I32P,
                                                                          _I32P, _F64P, ctypes.c_int])
         L.oc_oracle_batch_snapshot.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64] + [_I32P] * 7
+        L.oc_oracle_batch_last_step.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, _I32P]
         L.oc_oracle_batch_reset.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, _I32P]
         L.oc_oracle_pyset_order.argtypes = [_I32P, ctypes.c_int, _I32P]
         L.oc_oracle_debug_set.argtypes = [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P]
@@ -309,6 +310,29 @@ class OracleBatch:
             int(communication_on), int(ego_led), ego_agent_idx, can_move_mask, _p32(obs),
             _p64(ts), _p64(reward), _p32(done), int(auto_reset)))
         return obs, ts, reward, done
+
+    def last_step(self):
+        """What the last ``multi_step`` saw in every env before a possible auto-reset, int32 [n] each:
+        the sparse reward, ``successful``, the number of completed subtasks where the episode ended
+        (0 elsewhere), and whether the step raised an error flag -- the per-step terms of the
+        library's metrics counters (reward_sum, successes, completed_subtasks_sum, errors)."""
+        out = np.zeros((4, self.n), np.int32)
+        lib().oc_oracle_batch_last_step(self._handles, self.n, _p32(out))
+        return {"sparse": out[0], "success": out[1], "completed": out[2], "raised": out[3]}
+
+    def obs_image(self, radius):
+        """get_partial_observability_FOW of every env (``OracleEnv.obs_image``): maps int8
+        [2][7][W][H][n] and holding int32 [2][n] (every viewer reports both agents' hands)."""
+        W, H = int(self.blob[2]), int(self.blob[3])
+        maps = np.zeros((self.n, 2, 7, W, H), np.int8)
+        hold = np.zeros((self.n, 2), np.int32)
+        L = lib()
+        i8p = ctypes.POINTER(ctypes.c_int8)
+        for i in range(self.n):
+            for v in range(2):
+                L.oc_oracle_obs_image(self._handles[i], v, int(radius), maps[i, v].ctypes.data_as(i8p),
+                                      _p32(hold[i]))
+        return np.ascontiguousarray(np.moveaxis(maps, 0, -1)), np.ascontiguousarray(hold.T)
 
     def multi_rollout(self, actions, comm, radius, blind_mask, C, communication_on=True,
                       ego_led=False, ego_agent_idx=0, can_move_mask=3, auto_reset=True):

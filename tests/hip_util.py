@@ -54,5 +54,19 @@ def assert_snapshots_equal(hip, ora, ctx, where=None):
                                  % (ctx, k, bad, a[bad[0]], b[bad[0]]))
 
 
+SENTINEL, MARGIN = 0x5A, 4096            # guard bytes behind a tensor under test
+
+
+def with_margin(view):
+    """A tensor of `view`'s shape, dtype and contents at the start of a larger allocation whose
+    remaining bytes hold SENTINEL; returns (tensor, the margin bytes)."""
+    import torch
+    nb = view.numel() * view.element_size()
+    raw = torch.full((nb + MARGIN,), SENTINEL, dtype=torch.uint8, device=view.device)
+    t = raw[:nb].view(view.dtype).view(view.shape)
+    t.copy_(view)
+    return t, raw[nb:]
+
+
 def bits(x):
     return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)

@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 import torch
 
-from hip_util import bits
-from test_obs_tail_gpu import SENTINEL, _with_margin
+from hip_util import SENTINEL, bits
+from hip_util import with_margin as _with_margin
 
 pytestmark = pytest.mark.gpu
 

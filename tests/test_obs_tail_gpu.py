@@ -20,12 +20,12 @@ import numpy as np
 import pytest
 import torch
 
-from hip_util import bits, scripted_then_random
+from hip_util import SENTINEL, bits, scripted_then_random
+from hip_util import with_margin as _with_margin
 
 pytestmark = pytest.mark.gpu
 
 LEVEL, N, STEPS, RADIUS = "open-divider_tomato", 101, 40, 2
-SENTINEL, MARGIN = 0x5A, 4096            # bytes past the last row of each output tensor
 ORDERS = {"canonical": None, "permuted": [2, 0, 1]}
 DTYPES = {"int32": torch.int32, "int8": torch.int8, "float32": torch.float32}
 LAUNCHES = {"auto": None, "split4": "split=4", "split1": "split=1"}
@@ -60,16 +60,6 @@ def _reference(T, C, order):
     for a in (acts,) + tuple(x for s in steps for x in s):
         a.setflags(write=False)
     return acts, steps
-
-
-def _with_margin(view):
-    """A tensor of `view`'s shape, dtype and contents at the start of a larger allocation whose
-    remaining bytes hold SENTINEL; returns (tensor, the margin bytes)."""
-    nb = view.numel() * view.element_size()
-    raw = torch.full((nb + MARGIN,), SENTINEL, dtype=torch.uint8, device=view.device)
-    t = raw[:nb].view(view.dtype).view(view.shape)
-    t.copy_(view)
-    return t, raw[nb:]
 
 
 def _run(monkeypatch, T, C, order, dtype, launch):
