@@ -227,6 +227,9 @@ __device__ __forceinline__ void pack(const Env<A, M, DUP> &e, int32_t *w) {
 // an empty asm; otherwise InstCombine folds and/or of sign-extended compares back into i1 logic
 // and the backend selects the scalar unit again).
 typedef int P;
+// s_waitcnt vmcnt(0) as the operand of __builtin_amdgcn_s_waitcnt (gfx9 encoding: vmcnt in bits 3:0 and
+// 15:14, expcnt 6:4 and lgkmcnt 11:8 left at their maxima): a wait the compiler's wait-count pass sees
+constexpr int WAIT_VMCNT0 = 0x0F70;
 __device__ __forceinline__ int hide(int v) {
   asm("" : "+v"(v));
   return v;
@@ -236,11 +239,15 @@ __device__ __forceinline__ int hide(int v) {
 // wait states behind the compare (the 3-agent kernel carried 80 s_nop).  For operands in
 // [0, 2^31) -- every field of the packed state -- the sign of a difference is the predicate:
 // two plain, independent VALU instructions (v_xad_u32 / v_sub + v_ashrrev_i32), no vcc, no nop.
-__device__ __forceinline__ P p_z(int a) { return hide((int)((unsigned)a - 1u) >> 31); }              // a == 0   (a >= 0)
-__device__ __forceinline__ P p_nz(int a) { return hide((int)(0u - (unsigned)a) >> 31); }             // a != 0   (a >= 0)
-__device__ __forceinline__ P p_eq(int a, int b) { return hide((int)((unsigned)(a ^ b) - 1u) >> 31); }  // (bit 31 of a, b equal)
+// (The difference is hidden as well, in front of the shift: where the optimiser knows the operand's
+// range -- a masked field, a bit-field extract -- it proves the sign test equal to a compare with
+// zero and selects v_cmp + v_cndmask again, or a carry-out into vcc.)
+__device__ __forceinline__ P sign_of(int d) { return hide(hide(d) >> 31); }
+__device__ __forceinline__ P p_z(int a) { return sign_of((int)((unsigned)a - 1u)); }              // a == 0   (a >= 0)
+__device__ __forceinline__ P p_nz(int a) { return sign_of((int)(0u - (unsigned)a)); }             // a != 0   (a >= 0)
+__device__ __forceinline__ P p_eq(int a, int b) { return sign_of((int)((unsigned)(a ^ b) - 1u)); }  // (bit 31 of a, b equal)
 __device__ __forceinline__ P p_ne(int a, int b) { return ~p_eq(a, b); }
-__device__ __forceinline__ P p_lt(int a, int b) { return hide((a - b) >> 31); }                      // a < b    (0 <= a, b < 2^31)
+__device__ __forceinline__ P p_lt(int a, int b) { return sign_of(a - b); }                        // a < b    (0 <= a, b < 2^31)
 __device__ __forceinline__ P p_gt(int a, int b) { return p_lt(b, a); }
 __device__ __forceinline__ P p_ge(int a, int b) { return ~p_lt(a, b); }
 __device__ __forceinline__ P p_le(int a, int b) { return ~p_lt(b, a); }
@@ -249,7 +256,9 @@ __device__ __forceinline__ P p_eq_any(int a, int b) { return hide(a == b ? -1 : 
 __device__ __forceinline__ P p_gtu_any(unsigned a, unsigned b) { return hide(a > b ? -1 : 0); }
 __device__ __forceinline__ P p_geu_any(unsigned a, unsigned b) { return hide(a >= b ? -1 : 0); }
 __device__ __forceinline__ P p_ltu_any(unsigned a, unsigned b) { return hide(a < b ? -1 : 0); }
-__device__ __forceinline__ P p_bit(int w, unsigned k) { return __builtin_amdgcn_sbfe(w, k, 1u); }  // bit k as 0 / -1: one v_bfe_i32
+// bit k as 0 / -1: one v_bfe_i32 (hidden: a visible extract is re-derived where it is consumed, as
+// shift + compare + select in a `sel`, as and + compare under a `~`)
+__device__ __forceinline__ P p_bit(int w, unsigned k) { return hide(__builtin_amdgcn_sbfe(w, k, 1u)); }
 __device__ __forceinline__ P p_of(bool uniform) { return uniform ? -1 : 0; }                       // a wave-uniform condition
 __device__ __forceinline__ int sel(P m, int a, int b) { return (a & m) | (b & ~m); }               // v_bfi_b32
 
@@ -293,12 +302,22 @@ constexpr bool OC_BORDER_CLOSED = false;
 // without the 11-instruction fp64 division: q0 = t * RN(1/T), one FMA for the exact
 // residual, one FMA to correct.  Equal to the division for every 0 <= t, 1 <= T <= 65535
 // (all 4.3e9 pairs compared bit for bit: tests/test_host_cpu.py, tools/div_check.c).
+// No time limit (T == 0, uniform): t / 0.0, i.e. nan for t == 0 and inf otherwise, selected over the
+// quotient word by word under a uniform mask -- straight-line code, so that a caller can form the
+// value among its other arithmetic (as an early return it was three branches, and the kernels
+// carried the whole function behind their last row store).
 __device__ __forceinline__ double timestep_of(int t, const RunCfg &R) {
+  typedef int v2i __attribute__((ext_vector_type(2)));
   const double dt = (double)t;
-  if (R.T == 0) return t == 0 ? __builtin_nan("") : __builtin_inf();  // uniform; no time limit: t / 0.0
   const double q0 = dt * R.inv_T;
   const double r = __builtin_fma(-(double)R.T, q0, dt);
-  return __builtin_fma(r, R.inv_T, q0);
+  const v2i q = __builtin_bit_cast(v2i, __builtin_fma(r, R.inv_T, q0));
+  const P unlimited = p_of(R.T == 0);
+  const int hi0 = 0x7FF00000 | (p_z(t) & 0x00080000);   // inf; nan: the bits of __builtin_nan("")
+  v2i out;
+  out.x = q.x & ~unlimited;
+  out.y = sel(unlimited, hi0, q.y);
+  return __builtin_bit_cast(double, out);
 }
 
 
@@ -723,13 +742,22 @@ __device__ __forceinline__ void shaping_sum(const Hdr &L, const ShapeIn<B> &in, 
 // shaping (shaping_issue_*); the caller stores what it has to store and then calls
 // shaping_lookup(L, quot, sin, sld, sq) and, after its stores, shaping_sum(L, sin, sq, ...).
 // PM: arglist.play known at compile time (0 = off, 1 = on) or a run-time flag (2: R.play)
-template <int A, int M, bool DUP, int PM>
+// done_p: `done` as a P word, for the callers' auto-reset selects (formed from the 0 / 1 value it is
+// a compare again, and its AND with the uniform auto-reset flag a scalar read of vcc)
+// FLAT: a split workgroup's arm (one duty per wave): no uniform branch in the step, see `timeout`
+template <int A, int M, bool DUP, int PM, bool FLAT>
 __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const uint8_t *__restrict__ dist,
                                          const uint32_t *__restrict__ probe,
-                                         Env<A, M, DUP> &e, const int (&act_in)[A], int &reward, int &done,
+                                         Env<A, M, DUP> &e, const int (&act_in)[A], int &reward, int &done, P &done_p,
                                          int &success, ShapeIn<(A < 2 ? A : 2)> &sin,
                                          ShapeLoads<(A < 2 ? A : 2)> &sld OC_STAMP_PARAM) {
   const int W = L.W(), H = L.H();
+  // bit k as a P word: hidden (p_bit), except in the four-way split of the general variant (PM == 2),
+  // which allocates one VGPR more with the hidden form (profiles/step_prefix_ab.txt)
+  const auto pb = [](int w, unsigned k) -> P {
+    if constexpr (PM == 2 && FLAT) return __builtin_amdgcn_sbfe(w, k, 1u);
+    return p_bit(w, k);
+  };
   e.t = min(e.t + 1, 0xFFFF);  // :213 (16-bit field: saturates; max_num_timesteps <= 65535 is enforced)
   static_assert(OC_ACT_NOOP == 4 && OC_FLOOR == 0 && OC_COUNTER == 1 && OC_CUTBOARD == 2 && OC_DELIVERY == 3, "codes");
 
@@ -765,8 +793,8 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
     // tile type of the target cell as three predicates, straight from the bit-planes
     P lo, hi;
     if (!L.planes128()) {   // uniform (compile-time in specialised builds)
-      lo = p_bit((int)(L.cell_lo(0) >> cell), 0);
-      hi = p_bit((int)(L.cell_hi(0) >> cell), 0);
+      lo = pb((int)(L.cell_lo(0) >> cell), 0);
+      hi = pb((int)(L.cell_hi(0) >> cell), 0);
     } else {
       lo = -bit128(L.cell_lo(0), L.cell_lo(1), cell);
       hi = -bit128(L.cell_hi(0), L.cell_hi(1), cell);
@@ -805,7 +833,11 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
     // moves it), so the target cell and its tile type computed there still hold
     const int pa = e.ap[a];
     const int tp = tgt_p[a];
-    const P holding = p_nz(e.ahp[a]);
+    // held group (ahp - 1; -1 = empty hands): its sign is "not holding", and the subtraction is the
+    // one `newg` needs anyway (p_nz(ahp) on the extracted field came out as a carry into vcc + select)
+    // (two agents only: in the three- and four-agent kernels this form allocates one to two VGPRs more)
+    const int held_g = A == 2 ? hide(e.ahp[a] - 1) : e.ahp[a] - 1;
+    const P holding = A == 2 ? ~hide(held_g >> 31) : p_nz(e.ahp[a]);
     const int hold_code = (a + 1) << 12;
     // the held Object (items with holder == a) and the unheld Object on the target cell, as
     // ORs of their item words with bit 8 turned into "a food that is still fresh"
@@ -816,7 +848,7 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
       const int w = e.iw[i];
       const int u = item_type(L, i) != OC_PLATE ? (w ^ IW_CHOP) : w;  // uniform choice; a Plate is never chopped
       // (two agents: holder + 1 is 0, 1 or 2, so "held by agent a" is ONE bit of the word)
-      mine[i] = A == 2 ? p_bit(w, 12 + a) : p_eq(w & IW_HOLD, hold_code);
+      mine[i] = A == 2 ? pb(w, 12 + a) : p_eq(w & IW_HOLD, hold_code);
       tgt[i] = p_eq(w & (IW_HOLD | IW_POS), tp);                       // unheld and on the target cell
       held_or |= mine[i] & u;
       tgt_or |= tgt[i] & u;
@@ -831,8 +863,8 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
     } else {
       held_multi = p_nz(held_or & IW_TSET & ((held_or & IW_TSET) - (1 << 24)));
     }
-    const P held_fresh = p_bit(held_or, 8);
-    const P any_fresh = p_bit(held_or | tgt_or, 8);
+    const P held_fresh = pb(held_or, 8);
+    const P any_fresh = pb(held_or | tgt_or, 8);
     const P two_plates = p_nz((held_or & tgt_or) & sig_of_type<DUP>(OC_PLATE));
     const P at_deliv = t_deliv[a];
     const P nf = acting & t_nonfloor[a];
@@ -844,11 +876,12 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
     const P chop_here = t_cutb[a] & ~held_multi & held_fresh & ~play;                 // :52
     const P do_chop = nfh & ~tgt_any & chop_here;                                     // :52-54
     const P do_drop = nfh & ~tgt_any & ~chop_here;                                    // :56-57
-    const P chop_there = nfe & tgt_any & play & t_cutb[a] & p_bit(tgt_or, 8);         // :66-67 (a fresh food is always alone)
+    const P chop_there = nfe & tgt_any & play & t_cutb[a] & pb(tgt_or, 8);         // :66-67 (a fresh food is always alone)
     const P do_pick = nfe & tgt_any & ~chop_there & p_of(!((R.allergic >> a) & 1));   // :62-71, agent.py:296-298
     const P put = do_deliver | do_drop | (do_merge & play);
     const P take = (do_merge & ~play) | do_pick;
-    const int newg = min(sel(holding, e.ahp[a] - 1, 7), igrp(tgt_or));  // only used when `take` (then tgt_any)
+    // min(held group, or 7 with empty hands; group on the target cell): -1 is the largest unsigned
+    const int newg = (int)min((unsigned)held_g, (unsigned)igrp(tgt_or));  // only used when `take` (then tgt_any)
     // the merged Object: smallest item id as group, re-inserted under a new name = last in
     // world order (world.py:236-237), union of the type sets
     int objf;
@@ -998,8 +1031,8 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
 #pragma unroll
     for (int g = 0; g < MAX_GOALS; g++) {
       if (g < (int)L.ngoal()) {  // uniform
-        cnt_mask |= p_bit(present, L.goal_tset(g)) & (int)L.goal_nd(g);
-        del_mask |= p_bit(at_delivery, L.goal_tset(g)) & (int)L.goal_dl(g);
+        cnt_mask |= pb(present, L.goal_tset(g)) & (int)L.goal_nd(g);
+        del_mask |= pb(at_delivery, L.goal_tset(g)) & (int)L.goal_dl(g);
       }
     }
     newly = cnt_mask & ~e.goalcnt;  // goal count rose above goal_objects_count (:408-415)
@@ -1007,9 +1040,16 @@ __device__ __forceinline__ void env_step(const Hdr &L, const RunCfg &R, const ui
   reward = __popc(newly) + 3 * __popc(del_mask);  // Deliver pays +3 every step (:400-406)
   e.completed |= newly | del_mask;
   e.goalcnt = cnt_mask;
-  const P timeout = R.T != 0 ? p_ge(e.t, R.T) : 0;  // checked first (:245-249)
+  // checked first (:245-249).  No limit (T == 0, uniform): FLAT, compared with a value t never
+  // reaches (t is a 16-bit field) -- a uniform select of the operand, no branch round the compare.
+  // The one-wave kernels keep the branch: without it their code up to the first store is one
+  // scheduling region, and they allocate 2 to 4 VGPRs more (profiles/step_prefix_ab.txt).
+  P timeout;
+  if constexpr (FLAT) timeout = p_ge(e.t, R.T != 0 ? (int)R.T : 0x10000);
+  else timeout = R.T != 0 ? p_ge(e.t, R.T) : 0;
   const P all_delivered = p_eq_any(del_mask, (int)L.deliver_mask());   // (32-bit subtask masks)
-  done = (timeout | all_delivered) & 1;
+  done_p = hide(timeout | all_delivered);
+  done = done_p & 1;
   success = (~timeout & all_delivered) & 1;
 
   // ---- calculate_reward_shaping for sim agents 0 and 1 (:272-397): the rest of the inputs ----
@@ -1547,8 +1587,12 @@ __device__ __forceinline__ void step_body(int32_t *const state_, const int32_t *
     Env<A, M, DUP> e;
     unpack<A, M, DUP>(e, w);
     // split: no state row is stored before both waves hold their copy of the state
-    if constexpr (SPLIT) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    if constexpr (SPLIT) {
+      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(WAIT_VMCNT0);   // (every load is back: see multi_step_body)
+    }
     const int err_before = e.err;
+    P done_p = 0;
     constexpr int B = A < 2 ? A : 2;
     ShapeIn<B> sin;
     ShapeLoads<B> sld;
@@ -1557,7 +1601,7 @@ __device__ __forceinline__ void step_body(int32_t *const state_, const int32_t *
 #endif
     RunCfg R = p.R;
     R.T = T_;   // the preloaded copy
-    env_step<A, M, DUP, PLAY ? 1 : 0>(L, R, tb.dist, tb.probe, e, act, reward, done, success, sin, sld OC_STAMP_PASS);
+    env_step<A, M, DUP, PLAY ? 1 : 0, SPLIT>(L, R, tb.dist, tb.probe, e, act, reward, done, done_p, success, sin, sld OC_STAMP_PASS);
     comp = e.completed;
     err = e.err != err_before;
     ShapeQ<B> sq;
@@ -1567,7 +1611,7 @@ __device__ __forceinline__ void step_body(int32_t *const state_, const int32_t *
       Out(p.done, p.n, 1, i).st(0, done);
       if (L.nscatter() == 0) {   // uniform: a fixed level -- the fresh episode is a constant, selected word by word
         pack<A, M, DUP>(e, w);
-        const P fresh = -done & p_of(auto_reset_);
+        const P fresh = done_p & p_of(auto_reset_);
 #pragma unroll
         for (int r = 0; r < WS; r++) w[r] = sel(fresh, L.init_words(r), w[r]);
       } else if (done && auto_reset_) {
@@ -2022,6 +2066,14 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     const int F = 22 + L.S() + 2 * C;
     const Out ob(p.obs, p.n, 2 * F, i, OT == 1 ? 1 : 4);
     constexpr bool OBS_ONLY = SPLIT && (DUTY == DUTY_OBS0 || DUTY == DUTY_OBS1);
+    // which observation arm of a split workgroup stores the timestep (-DOC_TS_OBS1: viewer 1's, a
+    // measurement variant, profiles/step_prefix_ab.txt; with the policies fused always viewer 0's,
+    // which hands it to the policy passes)
+#ifdef OC_TS_OBS1
+    constexpr int TS_DUTY = POL ? DUTY_OBS0 : DUTY_OBS1;
+#else
+    constexpr int TS_DUTY = DUTY_OBS0;
+#endif
 #ifdef OC_SPECIALIZED
     // (the plain variant only, and at most 40 offsets -- salad's 22 + 9 + 8 fit beside the step's own
     // ~64 SGPRs; the options variants and a level with more subtasks began to spill SGPRs to VGPR
@@ -2040,7 +2092,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     [[maybe_unused]] const Parts parts(ob, slots, C);
 #endif
     const Out tso(p.timestep, p.n, 1, i, 8);
-    if constexpr (NPRE != 0 && DUTY == DUTY_OBS0) asm volatile("" ::"s"(tso.rsrc), "v"(tso.voff));
+    if constexpr (NPRE != 0 && DUTY == TS_DUTY) asm volatile("" ::"s"(tso.rsrc), "v"(tso.voff));
     // split: nothing that is updated in place -- state rows, the words of the random streams, the
     // done row the episode statistics read -- may be stored before every wave of the workgroup
     // holds its copy
@@ -2052,6 +2104,14 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
       if constexpr (XO != 0)
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" : "+v"(eq), "+v"(aq), "+v"(er), "+v"(ar), "+v"(alt_rs)::"memory");
       else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+      // The statement above has waited for every load, but the compiler's wait-count pass does not
+      // read asm text: it put an s_waitcnt vmcnt(N) in front of the first use of each loaded word in
+      // the decode below, up to nine of them, an issue slot each.  One wait it does see tells it that
+      // every load is back.
+      // (Tried: the words as "+v" operands of an empty statement behind the barrier, newest load
+      // first.  One wait in the observation arms, nine in the other two, where the scheduler issues
+      // the action loads first -- and the comm words the shaping arm never reads stayed alive.)
+      __builtin_amdgcn_s_waitcnt(WAIT_VMCNT0);
       // (the offsets pinned above hang on scalar loads, and this statement is ordered behind their
       // pins: left alone, the scheduler fills that latency with the step's arithmetic and the
       // barrier sinks ~400 instructions, to where the first store needs it)
@@ -2111,11 +2171,12 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     act[0] = cfg_ego_idx == 0 ? em : am;
     act[1] = cfg_ego_idx == 0 ? am : em;
     const int err_before = e.err;
+    P done_p = 0;
     e.err |= (bad_mv | bad_cm) & OC_ERR_ACTION;
     ShapeIn<2> sin;
     ShapeLoads<2> sld;
     // (the plain variant is only launched for play == 0; the general one reads the flag)
-    env_step<A, M, DUP, XO == 2 ? 2 : 0>(L, p.R, tb.dist, tb.probe, e, act, reward, done, success, sin, sld OC_STAMP_PASS);
+    env_step<A, M, DUP, XO == 2 ? 2 : 0, SPLIT>(L, p.R, tb.dist, tb.probe, e, act, reward, done, done_p, success, sin, sld OC_STAMP_PASS);
     comp = e.completed;
     err = e.err != err_before;
     if constexpr (D_STATE) {
@@ -2131,7 +2192,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
         // v_cmp -> s_and_saveexec, a scalar read of a vector-written mask (see `hide`).  (A wave that
         // goes on to the observations keeps the branch: it would have to unpack the words again.)
         pack<A, M, DUP>(e, w);
-        const P fresh = -done & p_of(p.auto_reset != 0);
+        const P fresh = done_p & p_of(p.auto_reset != 0);
 #pragma unroll
         for (int r = 0; r < WS; r++) w[r] = sel(fresh, L.init_words(r), w[r]);
       } else if (OBS_ONLY && L.nscatter() == 0) {
@@ -2142,7 +2203,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
         for (int r = 0; r < WS; r++) w0[r] = L.init_words(r);
         Env<A, M, DUP> e0;
         unpack<A, M, DUP>(e0, w0);
-        const P fresh = -done & p_of(p.auto_reset != 0);
+        const P fresh = done_p & p_of(p.auto_reset != 0);
 #pragma unroll
         for (int a = 0; a < A; a++) e.ap[a] = sel(fresh, e0.ap[a], e.ap[a]), e.ahp[a] = sel(fresh, e0.ahp[a], e.ahp[a]);
 #pragma unroll
@@ -2167,6 +2228,13 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
 #pragma unroll
       for (int r = 0; r < WS; r++) st.st(r, w[r]);
     }
+    // The timestep: formed here, where `t` is final, and -- in a split workgroup's observation arm --
+    // stored in front of the arm's rows, so that its fp64 chain runs under the observation's own
+    // arithmetic.  (It used to follow the last row store of viewer 0's arm, the longest.)
+    constexpr bool TS_MINE = OBS_ONLY ? DUTY == TS_DUTY : (DUTY & DUTY_OBS0) != 0;
+    [[maybe_unused]] double tsd = 0.0;
+    if constexpr (TS_MINE && OBS_ONLY && !POL) tsd = timestep_of(e.t, p.R);
+    if constexpr (TS_MINE && OBS_ONLY && !POL) tso.st_f64(0, tsd);
     ShapeQ<2> sq;
     if constexpr (D_SHAPE) shaping_lookup<2>(L, p.R.inv_max_path, sin, sld, sq OC_STAMP_PASS);
     const bool ego_blind = cfg_blind & 1;
@@ -2176,7 +2244,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
       if constexpr ((DUTY & DUTY_OBS0) != 0) {
         const RowsLdsT<WT ? AUX_WT : 0, OT> obl(ob, pol_lds_feat<POL_ROWS>(), 0, ln);
         env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obl, 0);
-        const double tsd = timestep_of(e.t, p.R);
+        const double tsd = timestep_of(e.t, p.R);   // (formed in place: held across the rows it costs registers)
         Out(p.timestep, p.n, 1, i, 8).st_f64(0, tsd);
         pol_lds_ts()[ln] = (float)tsd;
       }
@@ -2198,7 +2266,8 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
         if constexpr ((DUTY & DUTY_OBS1) != 0)
           env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obp, F);
       }
-      if constexpr ((DUTY & DUTY_OBS0) != 0) tso.st_f64(0, timestep_of(e.t, p.R));
+      // (a wave that does more than one viewer's rows: behind them, or the value would be held across both)
+      if constexpr (TS_MINE && !OBS_ONLY) tso.st_f64(0, timestep_of(e.t, p.R));
     }
     OC_STAMP(5);   // observation stores issued
     if constexpr (D_SHAPE) {
