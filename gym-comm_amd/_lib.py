@@ -103,6 +103,13 @@ def _libs_table():
             "oc_multi_step_prepare": (cint, multi_step + [P(vp)]),
             "oc_call_launch": (cint, [vp, vp, i32, vp]),
             "oc_call_destroy": (cint, [vp]),
+            # map sets (structure libraries): the set and the device group_map in the level's place
+            "oc_mapset_create": (cint, [P(_I32P), _I32P, i32, P(vp)]),
+            "oc_mapset_destroy": (cint, [vp]),
+            "oc_mapset_reset": (cint, [vp, vp, vp, vp, vp, vp, i64, vp]),
+            "oc_mapset_obs": (cint, [vp, vp, vp, vp, P(ObsCfg), vp, vp, i64, vp]),
+            "oc_mapset_multi_step": (cint, [vp] + multi_step + [vp]),
+            "oc_mapset_multi_step_waves": (i32, [i64, i32, i32]),
         }),
         "policy": Lib("OC_POLICY_LIB", "oc_policy_abi_version", 1, "oc_policy_last_error", {
             "oc_policy_abi_version": (cint, None),

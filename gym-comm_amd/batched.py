@@ -1,4 +1,5 @@
-"""BatchedOvercooked: N independent Overcooked envs of one level on one MI355X.
+"""BatchedOvercooked: N independent Overcooked envs of one level -- or, ``from_maps``, of several
+maps of one level structure -- on one MI355X.
 
 Host side of the hot path: owns the PyTorch-ROCm tensors (env-major int32 SoA) and calls
 the hand-written HIP kernels of liboc_hip.so through the C ABI (include/oc_hip.h) with
@@ -49,10 +50,12 @@ class BatchedOvercooked:
                  device="cuda", subtask_order=None, placements=None, level_dir=None,
                  max_num_subtasks=14, auto_reset=True, track_metrics=True, specialize_level="auto",
                  seed=0, placement_mode="rng", obs_dtype=torch.int32, episode_stats=False, play=False,
-                 waves_per_64=0):
+                 waves_per_64=0, _maps=None):
         cfg = {"ALLERGIC": False, "BLIND": False, "CAN_MOVE": True}   # missing CAN_MOVE = True
         self.ego_config = dict(cfg, **(ego_config or {}))
         self.partner_config = dict(cfg, **(partner_config or {}))
+        # a map set (from_maps): the compiled levels and the host copy of group_map; `level` is the first
+        self.levels, self.group_map_host = _maps if _maps is not None else (None, None)
         if isinstance(level, compiler.CompiledLevel):
             self.level = level
         else:
@@ -81,19 +84,38 @@ class BatchedOvercooked:
             raise ValueError("waves_per_64 must be 0 (auto), 1, 2 or 4")
         self.waves_per_64 = int(waves_per_64)
         blob = np.ascontiguousarray(lv.blob, dtype=np.int32)
-        # per-level specialised kernels when available (specialize.py), else the generic library
-        self.kernel_flavour, self._L = specialize.load_for(blob, specialize_level)
+        # per-level specialised kernels when available (specialize.py), else the generic library;
+        # a map set runs on the structure library its maps share
+        self.kernel_flavour, self._L = specialize.load_for(blob, "structure" if self.levels else specialize_level)
         # hipStream_t of torch's current stream on this env's device, as an int
         self._raw_stream = functools.partial(_lib.raw_stream, self._dev_index)
         h = ctypes.c_void_p()
-        self._call("oc_level_create", blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(blob.size),
-                   ctypes.byref(h), stream=False)
-        self._h = h
         # where the state keeps the bits of subtask s (the library's canonical subtask order)
         self.subtask_slot, self._goal_index, self._dup = _lib.subtask_info(blob, self._L)
-        self.W_state = self._L.oc_state_words(h)
-        self.F = self._L.oc_obs_rows(h, self.C)
         n = self.n
+        if self.levels:
+            # include/oc_hip.h, map sets: the set and the device group_map take the level's place in
+            # every call (self._lead); the entry points carry the same arguments otherwise
+            i32p = ctypes.POINTER(ctypes.c_int32)
+            blobs = [np.ascontiguousarray(m.blob, dtype=np.int32) for m in self.levels]
+            ptrs = (i32p * len(blobs))(*[b.ctypes.data_as(i32p) for b in blobs])
+            sizes = np.array([b.size for b in blobs], np.int32)
+            self._call("oc_mapset_create", ptrs, sizes.ctypes.data_as(i32p), len(blobs), ctypes.byref(h), stream=False)
+            self._h = h
+            self.group_map = torch.from_numpy(self.group_map_host).to(self.device)
+            self._lead = (self._h, self.group_map.data_ptr())
+            self._fn = {k: "oc_mapset_" + k for k in ("reset", "obs", "multi_step", "multi_step_waves")}
+            self.W_state = self.A + self.M + 2 + (2 if self._dup else 0)
+            self.F = 22 + self.S + 2 * self.C
+        else:
+            self._call("oc_level_create", blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(blob.size),
+                       ctypes.byref(h), stream=False)
+            self._h = h
+            self.group_map = None
+            self._lead = (self._h,)
+            self._fn = {k: "oc_" + k for k in ("reset", "obs", "multi_step", "multi_step_waves")}
+            self.W_state = self._L.oc_state_words(h)
+            self.F = self._L.oc_obs_rows(h, self.C)
         if obs_dtype not in OBS_TYPE:
             raise ValueError("obs_dtype must be torch.int32, torch.int8 or torch.float32")
         # Every tensor a step reads or writes is a view of ONE device allocation (each view
@@ -151,8 +173,119 @@ class BatchedOvercooked:
         self._calls = []
         h = getattr(self, "_h", None)
         if h is not None and h.value:
-            self._L.oc_level_destroy(h)
+            (self._L.oc_mapset_destroy if self.levels else self._L.oc_level_destroy)(h)
             self._h = None
+
+    # -- map sets ----------------------------------------------------------------
+    @classmethod
+    def from_maps(cls, levels, group_map=None, envs_per_map=None, num_envs=None, num_agents=2,
+                  max_num_timesteps=100, max_num_subtasks=14, subtask_order=None, level_dir=None, play=False,
+                  policy=None, **kw):
+        """Envs on DIFFERENT maps of one level structure, stepped by one launch (include/oc_hip.h: map
+        sets).  ``levels``: level names or ``CompiledLevel`` objects whose structure (recipes, item
+        multiset, 2 agents, border kind) and subtask order are equal; the batch runs on the structure
+        library of the first.  Envs are assigned in GROUPS of 64 -- envs 64 g ... 64 g + 63 live on map
+        ``group_map[g]`` -- for the life of the batch:
+          ``group_map``     one map index per group, ``ceil(num_envs / 64)`` of them, or
+          ``envs_per_map``  an env count per map, in map order: multiples of 64 (only the last
+                            group of the batch may be partial, so only the last count may not be), or
+          neither           the ``num_envs`` envs' groups are dealt round-robin.
+        Every other keyword is ``BatchedOvercooked``'s.  Everything is validated here, before any GPU
+        call.  The batch has the single-level surface -- ``reset``, ``observe``, ``multi_step`` with rows,
+        pairs, the in-kernel partner and episode statistics, ``fetch``, ``get_state`` / ``set_state`` --
+        except the base ``step``, ``observe_image`` and the fused policies (``policy=`` raises); a launch
+        hint the set kernels have no variant for (``waves_per_64=2``) gets the nearest launch there is;
+        ``map_of(i)`` names env i's level and ``read_metrics()`` adds the counters per map."""
+        if policy is not None:
+            raise ValueError("from_maps: the fused policies (policy=) are not available for map sets")
+        if num_agents != 2:
+            raise ValueError("from_maps: map sets step exactly 2 agents")
+        if not levels:
+            raise ValueError("from_maps: need at least one level")
+        cfg = {"ALLERGIC": False}
+        ego, partner = dict(cfg, **(kw.get("ego_config") or {})), dict(cfg, **(kw.get("partner_config") or {}))
+        lvs = [m if isinstance(m, compiler.CompiledLevel) else
+               compiler.compile_level(m, 2, max_num_timesteps, max_num_subtasks, ego_allergic=ego["ALLERGIC"],
+                                      partner_allergic=partner["ALLERGIC"], subtask_order=subtask_order,
+                                      level_dir=level_dir, play=play) for m in levels]
+        first = lvs[0]
+        want = specialize.spec_header_text(first.blob, geometry=False), _lib.subtask_info(first.blob)
+        for m in lvs:
+            if not m.hip_supported or m.num_agents != 2:
+                raise ValueError("from_maps: level %r is not a 2-agent level the HIP path supports" % m.name)
+            got = specialize.spec_header_text(m.blob, geometry=False), _lib.subtask_info(m.blob)
+            if got[0] != want[0]:
+                raise ValueError("from_maps: levels %r and %r differ in structure (recipes, item multiset, agent "
+                                 "count, border kind): a map set needs one structure" % (first.name, m.name))
+            if got[1] != want[1] or bool(m.play) != bool(first.play):
+                raise ValueError("from_maps: levels %r and %r differ in subtask order or `play`" % (first.name, m.name))
+        K = len(lvs)
+        if group_map is not None and envs_per_map is not None:
+            raise ValueError("from_maps: pass group_map or envs_per_map, not both")
+        if envs_per_map is not None:
+            counts = [int(c) for c in envs_per_map]
+            if len(counts) != K or any(c < 0 for c in counts):
+                raise ValueError("from_maps: envs_per_map needs one non-negative count per level")
+            if any(c % 64 for c in counts[:-1]):
+                raise ValueError("from_maps: envs_per_map counts must be multiples of 64 (envs are assigned in groups "
+                                 "of 64; only the last group of the batch may be partial): got %s" % counts)
+            if num_envs is not None and int(num_envs) != sum(counts):
+                raise ValueError("from_maps: num_envs disagrees with envs_per_map")
+            num_envs = sum(counts)
+            gm = np.concatenate([np.full((c + 63) // 64, m, np.int32) for m, c in enumerate(counts)])
+        else:
+            if num_envs is None:
+                raise ValueError("from_maps: pass num_envs (with group_map, or alone) or envs_per_map")
+            num_envs = int(num_envs)
+            groups = (num_envs + 63) // 64
+            if group_map is None:
+                gm = (np.arange(groups) % K).astype(np.int32)
+            else:
+                gm = np.asarray(group_map)
+                if gm.ndim != 1 or gm.size != groups or gm.dtype.kind not in "iu":
+                    raise ValueError("from_maps: group_map must hold one map index per group of 64 envs: %d for %d "
+                                     "envs (got shape %s)" % (groups, num_envs, gm.shape))
+                if gm.size and (gm.min() < 0 or gm.max() >= K):
+                    raise ValueError("from_maps: group_map values must lie in 0..%d (got %d..%d)"
+                                     % (K - 1, gm.min(), gm.max()))
+                gm = gm.astype(np.int32)
+        if num_envs < 1:
+            raise ValueError("from_maps: no envs")
+        full = {"BLIND": False, "CAN_MOVE": True}
+        players = [dict(full, **(kw.get(c) or {})) for c in ("ego_config", "partner_config")]
+        std = (kw.get("communication_on", True) and not kw.get("ego_led", False) and kw.get("ego_agent_idx", 0) == 0
+               and not first.play and all(c["CAN_MOVE"] and not c["BLIND"] for c in players))
+        if not std:
+            raise ValueError("from_maps: map sets run the wrapper's standard configuration (communication on, not "
+                             "ego-led, both CAN_MOVE, ego_agent_idx 0, nobody BLIND, play off)")
+        return cls(first, num_agents=2, num_envs=num_envs, _maps=(lvs, np.ascontiguousarray(gm)), **kw)
+
+    def map_of(self, i):
+        """Name of the level env i lives on."""
+        if not 0 <= int(i) < self.n:
+            raise IndexError("env index %d outside 0..%d" % (i, self.n - 1))
+        return (self.levels[int(self.group_map_host[int(i) // 64])] if self.levels else self.level).name
+
+    def level_of(self, i):
+        """The ``CompiledLevel`` env i lives on."""
+        return self.levels[int(self.group_map_host[int(i) // 64])] if self.levels else self.level
+
+    def _single_level_only(self, what):
+        if self.levels:
+            raise ValueError("%s is not available for a map set (BatchedOvercooked.from_maps)" % what)
+
+    def get_state(self):
+        """Everything that carries the batch from one step to the next -- the arena (state, comm, done,
+        outputs, episode statistics), the placement stream and the metrics -- as device copies."""
+        cl = lambda t: None if t is None else t.clone()
+        return {"arena": self._arena.clone(), "rng": cl(self.rng), "metrics": cl(self.metrics)}
+
+    def set_state(self, st):
+        """Put a ``get_state()`` of this batch (or of one of the same shape) back."""
+        self._arena.copy_(st["arena"])
+        for name in ("rng", "metrics"):
+            if getattr(self, name) is not None:
+                getattr(self, name).copy_(st[name])
 
     @property
     def launch_waves_per_64(self):
@@ -174,11 +307,13 @@ class BatchedOvercooked:
         oc_multi_step_waves): the plain step, or -- ``general`` -- the general variant (pairs /
         in-kernel partner / episode statistics / policies / a non-standard wrapper configuration:
         what ``OvercookedVecEnv`` launches), which splits four ways or not at all."""
-        return int(self._L.oc_multi_step_waves(self.n, self.waves_per_64, 1 if general else 0))
+        return int(getattr(self._L, self._fn["multi_step_waves"])(self.n, self.waves_per_64, 1 if general else 0))
 
     def launch_lanes(self, general=False):
         """Lanes per env of that launch (include/oc_hip.h: oc_multi_step_lanes): 1, or 2 where
         the library lane-splits the plain step's four-way split at a small batch."""
+        if self.levels:
+            return 1
         return int(self._L.oc_multi_step_lanes(self.n, self.waves_per_64, 1 if general else 0))
 
     # -- helpers ---------------------------------------------------------------
@@ -209,7 +344,7 @@ class BatchedOvercooked:
         """Reset all envs, or those with mask[n] != 0 (int32 [n])."""
         if mask is not None:
             self._check_tensor(mask, (self.n,), torch.int32, "mask")
-        self._call("oc_reset", self._h, self._p(self.state), self._p(mask), self._p(self.placement),
+        self._call(self._fn["reset"], *self._lead, self._p(self.state), self._p(mask), self._p(self.placement),
                    self._p(self.rng), self.n)
 
     def set_placement(self, placement: torch.Tensor):
@@ -224,6 +359,7 @@ class BatchedOvercooked:
         """Base-env step.  actions: int32 [A][n] action codes 0..4 (4 = stay).
         Returns (reward int32[n], done int32[n], shaping f64[2][n]) -- views of
         pre-allocated tensors, overwritten by the next call."""
+        self._single_level_only("the base step")
         self._check_tensor(actions, (self.A, self.n), torch.int32, "actions")
         ar = self.auto_reset if auto_reset is None else auto_reset
         self._call("oc_step", self._h, self._p(self.state), self._p(actions), self._p(self.reward),
@@ -234,7 +370,7 @@ class BatchedOvercooked:
     def observe(self):
         """Both viewers' observations of the current state.  Returns (obs int32 [2][F][n],
         timestep f64 [n])."""
-        self._call("oc_obs", self._h, self._p(self.state), self._p(self.comm), ctypes.byref(self._obs_cfg),
+        self._call(self._fn["obs"], *self._lead, self._p(self.state), self._p(self.comm), ctypes.byref(self._obs_cfg),
                    self._p(self.obs), self._p(self.timestep), self.n)
         return self.obs, self.timestep
 
@@ -270,6 +406,7 @@ class BatchedOvercooked:
             self._check_tensor(alt_played, (2, n), torch.int32, "alt_played")
         ptr = lambda t: None if t is None else t.data_ptr()
         if policy is not None:
+            self._single_level_only("policy= (the fused policies)")
             if ego_pairs is None or alt_pairs is None or pdt is not torch.int32 or alt_rng is not None:
                 raise ValueError("policy= needs int32 ego_pairs and alt_pairs (it overwrites them) and no alt_rng")
             if self._policy_arr is None:
@@ -290,24 +427,26 @@ class BatchedOvercooked:
             dp = lambda t: 0 if t is None else t.data_ptr()
             self._ms_opts = _lib.StepOpts(dp(self.ep_return) or None, dp(self.ep_length) or None,
                                           None, None, None, None, 0, self.waves_per_64)
-            a = self._ms_args = [self._h, dp(self.state), dp(self.comm), 0, ctypes.byref(self._wrap_cfg),
+            a = self._ms_args = [*self._lead, dp(self.state), dp(self.comm), 0, ctypes.byref(self._wrap_cfg),
                                  dp(self.obs), dp(self.timestep), dp(self.shaped_reward), dp(self.done),
                                  dp(self.reward), 0, dp(self.metrics), dp(self.placement), dp(self.rng),
                                  ctypes.byref(self._ms_opts), self.n, 0]
+            self._ms_fn = getattr(self._L, self._fn["multi_step"])
         o = self._ms_opts
+        k = len(self._lead) - 1     # (a map set's calls carry group_map behind the handle)
         o.ego_pairs, o.alt_pairs, o.alt_rng, o.alt_played = ego_pairs_ptr, alt_pairs_ptr, alt_rng_ptr, alt_played_ptr
         o.pairs_int64 = 1 if pairs_int64 else 0
         o.policy = policy if policy is not None else None    # (_lib.StepPolicy * 2) or NULL
-        a[3] = actions_ptr
-        a[10] = auto_reset
-        a[16] = self._raw_stream()
+        a[3 + k] = actions_ptr
+        a[10 + k] = auto_reset
+        a[16 + k] = self._raw_stream()
         if torch.cuda.current_device() == self._dev_index:
-            rc = self._L.oc_multi_step(*a)
+            rc = self._ms_fn(*a)
         else:
             with torch.cuda.device(self.device):
-                rc = self._L.oc_multi_step(*a)
+                rc = self._ms_fn(*a)
         if rc:
-            _lib.check(rc, "oc_multi_step", self._L)
+            _lib.check(rc, self._fn["multi_step"], self._L)
 
     def prepare_multi_step(self, actions_ptr, alt_rng_ptr=None, alt_played_ptr=None, alt_pairs_ptr=None,
                            auto_reset=True):
@@ -315,6 +454,11 @@ class BatchedOvercooked:
         pair tensor fixed once; returns ``launch(ego_pairs_ptr_or_None, pairs_int64)`` whose per-call
         cost is a 4-argument foreign call (the 17-argument one costs a Python caller ~2 us more)."""
         dp = lambda t: 0 if t is None else t.data_ptr()
+        if self.levels:     # (no prepared form for map sets: the same launch through multi_step_raw)
+            def launch_set(ego_pairs_ptr=None, pairs_int64=False):
+                self.multi_step_raw(actions_ptr or 0, ego_pairs_ptr, alt_pairs_ptr, alt_rng_ptr, alt_played_ptr,
+                                    int(auto_reset), pairs_int64)
+            return launch_set
         opts = _lib.StepOpts(dp(self.ep_return) or None, dp(self.ep_length) or None, None, alt_pairs_ptr,
                              alt_rng_ptr, alt_played_ptr, 0, self.waves_per_64)
         h = ctypes.c_void_p()
@@ -344,6 +488,7 @@ class BatchedOvercooked:
         cells of a plane of an env per dword ([2][7*ceil(WH/4)][n] int32, include/oc_hip.h); the
         [2][7][W][H][n] result is one re-layout copy of that -- `packed=True` returns the
         kernel's tensor itself."""
+        self._single_level_only("observe_image")
         lv = self.level
         if getattr(self, "_image", None) is None:
             self._image_words = self._L.oc_image_words(self._h)
@@ -414,6 +559,13 @@ class BatchedOvercooked:
     def read_metrics(self):
         if self.metrics is None:
             return None
-        m = self.metrics_vector().cpu().tolist()
-        return {"env_steps": m[0], "episodes": m[1], "successes": m[2], "reward_sum": m[3],
-                "completed_subtasks_sum": m[4], "errors": m[5]}
+        name = lambda m: {"env_steps": m[0], "episodes": m[1], "successes": m[2], "reward_sum": m[3],
+                          "completed_subtasks_sum": m[4], "errors": m[5]}
+        if not self.levels:
+            return name(self.metrics_vector().cpu().tolist())
+        # a map set: one slot per group of 64 envs, so a map's counters are the sum of its groups' slots
+        slots = self.metrics.cpu().numpy()[:self.group_map_host.size]
+        out = name(slots.sum(axis=0).tolist())
+        out["per_map"] = [dict(name(slots[self.group_map_host == m].sum(axis=0).tolist()), level=lv.name)
+                          for m, lv in enumerate(self.levels)]
+        return out

@@ -65,6 +65,15 @@ struct oc_level {
   int device;
 };
 
+// A map set (oc_mapset_create): K maps of this structure library's structure
+struct oc_mapset {
+  int32_t k;
+  LevelHdr hdr;     // blob 0's: what the set shares -- S, M, the dup flag, the scatter count
+  uint32_t play;    // RunCfg.play, equal across the set
+  void *dev;        // K MapRecords, then the maps' table images (oc_step_device.h: MapRecord)
+  int device;
+};
+
 // A prepared oc_multi_step (oc_multi_step_prepare): every argument by value
 struct oc_call {
   const oc_level *lv;
@@ -675,6 +684,188 @@ int32_t oc_multi_step_waves(int64_t n, int32_t hint, int32_t general_variant) {
 
 int32_t oc_multi_step_lanes(int64_t n, int32_t hint, int32_t general_variant) {
   return select_multi(0, general_variant != 0, false, false, hint, n).ln;
+}
+
+// ---- map sets (structure libraries; oc_step_device.h: k_mapset_*) -------------------------------
+#if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
+namespace {
+int fail_at(int index, const char *what, const char *msg) {
+  snprintf(g_err, sizeof(g_err), "%s: blob %d: %s", what, index, msg);
+  return OC_E_BADARG;
+}
+// a set launch: always one group of 64 envs per workgroup, on `sp` waves
+Shape set_shape(int sp) { return {64, 64 * sp}; }
+// Waves per 64 envs of a set's fused step: the policy's or the caller's wish (split_for), brought to
+// the nearest launch the set kernels have -- one wave, or the four-way split (two -> four)
+int set_split_for(int64_t n, int hint) { return split_for(n, hint) == 1 ? 1 : 4; }
+}  // namespace
+#endif
+
+int oc_mapset_create(const int32_t *const *blobs, const int32_t *n_words, int32_t k, oc_mapset_t **out) {
+#if !defined(OC_SPECIALIZED)
+  (void)blobs, (void)n_words, (void)k, (void)out;
+  return fail(OC_E_BADARG, "oc_mapset_create: map sets need a structure library (this is the generic one)");
+#elif defined(OC_SPEC_GEOMETRY)
+  (void)blobs, (void)n_words, (void)k, (void)out;
+  return fail(OC_E_BADARG, "oc_mapset_create: map sets need a structure library (this is a level library: one map folded in)");
+#else
+  if (!out || !blobs || !n_words) return fail(OC_E_BADARG, "oc_mapset_create: null pointer");
+  if (k < 1) return fail(OC_E_BADARG, "oc_mapset_create: a map set holds at least one map (k < 1)");
+  std::vector<MapRecord> recs;
+  std::vector<uint8_t> image, img;
+  oc_mapset *ms = nullptr;
+  try {
+    recs.resize((size_t)k);
+    const size_t rec_bytes = ((size_t)k * sizeof(MapRecord) + 15) & ~(size_t)15;
+    image.assign(rec_bytes, 0);
+    for (int32_t m = 0; m < k; m++) {
+      MapRecord &r = recs[(size_t)m];
+      memset(&r, 0, sizeof(r));
+      const char *msg = build_header(blobs[m], n_words[m], r.L, r.R);
+      if (msg) return fail_at(m, "oc_mapset_create", msg);
+      const LevelHdr spec = OC_SPEC_HDR, mine = structure_of(r.L), first = structure_of(recs[0].L);
+      if (memcmp(&spec, &mine, sizeof(LevelHdr)) != 0)
+        return fail_at(m, "oc_mapset_create", "its structure (recipes, item multiset, agent count, border kind) is not this library's");
+      if (memcmp(&first, &mine, sizeof(LevelHdr)) != 0)
+        return fail_at(m, "oc_mapset_create", "its structure differs from blob 0's");
+      if (r.L.A != 2) return fail_at(m, "oc_mapset_create", "map sets step exactly 2 agents");
+      if (r.R.slot_identity != recs[0].R.slot_identity || memcmp(r.R.slot4, recs[0].R.slot4, sizeof(r.R.slot4)) != 0)
+        return fail_at(m, "oc_mapset_create", "its subtask order differs from blob 0's");
+      if (r.R.play != recs[0].R.play) return fail_at(m, "oc_mapset_create", "its `play` flag differs from blob 0's");
+      msg = build_tables(blobs[m], r.L, img);
+      if (msg) return fail_at(m, "oc_mapset_create", msg);
+      r.tab_off = (int64_t)image.size();
+      r.n16 = (int32_t)(img.size() / 16);
+      image.insert(image.end(), img.begin(), img.end());   // (a multiple of 16 bytes: every image stays aligned)
+    }
+    ms = new oc_mapset();
+  } catch (const std::bad_alloc &) {
+    return fail(OC_E_BADARG, "oc_mapset_create: out of memory");
+  }
+  ms->k = k;
+  ms->hdr = recs[0].L;
+  ms->play = recs[0].R.play;
+  ms->dev = nullptr;
+  hipError_t e = hipGetDevice(&ms->device);
+  if (e == hipSuccess) e = hipMalloc(&ms->dev, image.size());
+  if (e == hipSuccess) {   // (the records carry their table image's device address)
+    for (int32_t m = 0; m < k; m++) recs[(size_t)m].tables = (const char *)ms->dev + recs[(size_t)m].tab_off;
+    memcpy(image.data(), recs.data(), (size_t)k * sizeof(MapRecord));
+    e = hipMemcpy(ms->dev, image.data(), image.size(), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    oc_mapset_destroy(ms);
+    fail_hip(e, "oc_mapset_create");
+    return OC_E_NODEVICE;
+  }
+  *out = ms;
+  return OC_OK;
+#endif
+}
+
+int oc_mapset_destroy(oc_mapset_t *ms) {
+  if (!ms) return OC_OK;
+  if (ms->dev) (void)hipFree(ms->dev);
+  delete ms;
+  return OC_OK;
+}
+
+int oc_mapset_reset(const oc_mapset_t *ms, const int32_t *group_map, int32_t *state, const int32_t *mask,
+                    const int32_t *placement, uint32_t *rng, int64_t n, void *stream) {
+#if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
+  if (ms && group_map && n == 0) return OC_OK;
+  if (!ms || !group_map || !state || n < 0) return fail(OC_E_BADARG, "oc_mapset_reset: bad argument");
+  if (ms->hdr.nscatter > 0 && !placement && !rng)
+    return fail(OC_E_BADARG, "oc_mapset_reset: these maps place items at random; pass `placement` or `rng`");
+  const SetResetArgs a{(const MapRecord *)ms->dev, group_map, state, mask, placement, rng, n};
+  return no_kernel(lift([&](auto M, auto D) { return launch(k_mapset_reset<M, D>, set_shape(1), n, 0, stream, a); },
+                        Items{ms->hdr.M}, Dup{ms->hdr.has_dup != 0}),
+                   NO_AM);
+#else
+  (void)ms, (void)group_map, (void)state, (void)mask, (void)placement, (void)rng, (void)n, (void)stream;
+  return fail(OC_E_BADARG, "oc_mapset_reset: map sets need a structure library");
+#endif
+}
+
+int oc_mapset_obs(const oc_mapset_t *ms, const int32_t *group_map, const int32_t *state, const int32_t *comm,
+                  const oc_obs_cfg *cfg, void *obs, double *timestep, int64_t n, void *stream) {
+#if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
+  if (ms && group_map && cfg && n == 0) return OC_OK;
+  if (!ms || !group_map || !state || !comm || !cfg || !obs || !timestep || n < 0 || cfg->num_comm < 0 ||
+      cfg->num_comm > 128)
+    return fail(OC_E_BADARG, "oc_mapset_obs: bad argument");
+  if (!fits_buffer(n, 2 * (22 + ms->hdr.S + 2 * cfg->num_comm), 4))
+    return fail(OC_E_BADARG, "oc_mapset_obs: n too large for one call (tensor rows are addressed with 32-bit offsets); split the batch");
+  if (cfg->obs_int8 < 0 || cfg->obs_int8 > 2)
+    return fail(OC_E_BADARG, "oc_mapset_obs: obs_int8 must be 0 (int32), 1 (int8) or 2 (float32)");
+  const SetObsArgs a{(const MapRecord *)ms->dev, group_map, state, comm, obs, timestep, n, *cfg};
+  return no_kernel(lift([&](auto M, auto D, auto OT) { return launch(k_mapset_obs<M, OT, D>, set_shape(1), n, 0, stream, a); },
+                        Items{ms->hdr.M}, Dup{ms->hdr.has_dup != 0}, ObsType{cfg->obs_int8}),
+                   NO_AM);
+#else
+  (void)ms, (void)group_map, (void)state, (void)comm, (void)cfg, (void)obs, (void)timestep, (void)n, (void)stream;
+  return fail(OC_E_BADARG, "oc_mapset_obs: map sets need a structure library");
+#endif
+}
+
+int oc_mapset_multi_step(const oc_mapset_t *ms, const int32_t *group_map, int32_t *state, int32_t *comm,
+                         const int32_t *actions, const oc_wrap_cfg *cfg, void *obs, double *timestep,
+                         double *reward, int32_t *done, int32_t *sparse, int32_t auto_reset, int64_t *metrics,
+                         const int32_t *placement, uint32_t *rng, const oc_step_opts *opts, int64_t n,
+                         void *stream) {
+#if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
+  if (ms && group_map && cfg && n == 0) return OC_OK;
+  oc_step_opts o;
+  memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  if ((o.ep_return == nullptr) != (o.ep_length == nullptr))
+    return fail(OC_E_BADARG, "oc_mapset_multi_step: pass both ep_return and ep_length, or neither");
+  if (!actions && !(o.ego_pairs && (o.alt_pairs || o.alt_rng)))
+    return fail(OC_E_BADARG, "oc_mapset_multi_step: no `actions` and no complete replacement in `opts`");
+  if (!ms || !group_map || !state || !comm || !cfg || !obs || !timestep || !reward || !done || n < 0 ||
+      cfg->obs.num_comm < 0 || cfg->obs.num_comm > 128)
+    return fail(OC_E_BADARG, "oc_mapset_multi_step: bad argument");
+  if (o.policy) return fail(OC_E_BADARG, "oc_mapset_multi_step: opts.policy (the fused policies) is not available for map sets");
+  if (!fits_buffer(n, 2 * (22 + ms->hdr.S + 2 * cfg->obs.num_comm), 4) || !fits_buffer(n, 1, 16))
+    return fail(OC_E_BADARG, "oc_mapset_multi_step: n too large for one call (tensor rows are addressed with 32-bit offsets); split the batch");
+  if (auto_reset && ms->hdr.nscatter > 0 && !placement && !rng)
+    return fail(OC_E_BADARG, "oc_mapset_multi_step: auto_reset on random-placement maps needs `placement` or `rng`");
+  const int ot = cfg->obs.obs_int8;
+  if (ot < 0 || ot > 2) return fail(OC_E_BADARG, "oc_mapset_multi_step: obs_int8 must be 0 (int32), 1 (int8) or 2 (float32)");
+  const MapRecord *maps = (const MapRecord *)ms->dev;
+  const bool std_cfg = cfg->communication_on && !cfg->ego_led && cfg->can_move_mask == 3 &&
+                       cfg->ego_agent_idx == 0 && cfg->obs.blind_mask == 0 && !ms->play;
+  if (!std_cfg)
+    return fail(OC_E_BADARG, "oc_mapset_multi_step: map sets run the wrapper's standard configuration (communication on, "
+                             "not ego-led, both CAN_MOVE, ego_agent_idx 0, nobody BLIND, play off)");
+  const int xo = (o.ep_return || o.ego_pairs || o.alt_pairs || o.alt_rng) ? 1 : 0;
+  const int sp = set_split_for(n, o.waves_per_64);
+  const SetMultiArgs a{maps, group_map, obs, timestep, reward, done, sparse, placement, rng, o, n, auto_reset, *cfg};
+  const int32_t src = (o.ego_pairs ? 1 : 0) | (o.alt_pairs ? 2 : 0) | (o.alt_rng ? 4 : 0) | (o.pairs_int64 ? 8 : 0);
+  const int32_t block_ = 64 | (src << 16);
+  const void *const alt_src = o.alt_rng ? (const void *)o.alt_rng : (const void *)o.alt_pairs;
+  return no_kernel(lift([&](auto M, auto D, auto OT, auto XO, auto SP) {
+                          return launch(k_mapset_step<M, OT, D, XO, SP>, set_shape(sp), n, 0, stream, state, actions, comm,
+                                        metrics, (int32_t)n, block_, (const void *)o.ego_pairs, alt_src, a);
+                        },
+                        Items{ms->hdr.M}, Dup{ms->hdr.has_dup != 0}, ObsType{ot}, Among<int, 0, 1>{xo},
+                        Among<int, 1, 4>{sp}),
+                   "oc_mapset_multi_step: unsupported number of items");
+#else
+  (void)ms, (void)group_map, (void)state, (void)comm, (void)actions, (void)cfg, (void)obs, (void)timestep, (void)reward;
+  (void)done, (void)sparse, (void)auto_reset, (void)metrics, (void)placement, (void)rng, (void)opts, (void)n, (void)stream;
+  return fail(OC_E_BADARG, "oc_mapset_multi_step: map sets need a structure library");
+#endif
+}
+
+int32_t oc_mapset_multi_step_waves(int64_t n, int32_t hint, int32_t general_variant) {
+  (void)general_variant;   // (XO = 0 and 1 have the same launches)
+#if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
+  return set_split_for(n, hint);
+#else
+  (void)n, (void)hint;
+  return 0;   // no set kernels in this library
+#endif
 }
 
 int oc_random_actions(uint32_t *rng, int32_t *move_row, int32_t *comm_row, int32_t num_comm, int64_t n,

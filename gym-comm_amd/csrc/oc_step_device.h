@@ -1475,6 +1475,25 @@ __device__ __forceinline__ Tables stage_tables(const void *__restrict__ tables, 
   return tb;
 }
 
+// The map a wave's envs live on -- header, run configuration, table image -- as REFERENCES, so that each
+// word is fetched where the code first needs it.  The launch's own (the by-value kernel argument:
+// k_multi_step, k_obs, k_reset) or, in a map set, the record of the workgroup's map (k_mapset_*).
+struct MapRef {
+  const LevelHdr &L;
+  const RunCfg &R;
+  const void *const &tables;
+  const int32_t &n16;
+};
+// Where a step finds its MapRef.  ref(): valid anywhere; ref_behind_loads(): called once, where the
+// step has issued its state and action loads -- a map set looks its group's record up there and not
+// before, so that those loads never wait for it.  LaunchMap: the launch's own map, the same references
+// at both places.
+struct LaunchMap {
+  MapRef mp;
+  __device__ __forceinline__ MapRef ref() const { return mp; }
+  __device__ __forceinline__ MapRef ref_behind_loads() const { return mp; }
+};
+
 // Start cells of the items for a fresh episode of a random-* level
 // (overcooked_environment.py:157-173: for every scattered letter, random.choice over ALL
 // Counter tiles until one not yet taken by this phase comes up).  Either read from the
@@ -1671,10 +1690,11 @@ struct ObsArgs {
   oc_obs_cfg cfg;
 };
 
-template <int A, int M, int OT, bool WT, bool DUP>
-__global__ void __launch_bounds__(256) k_obs(const ObsArgs p) {
+// both viewers' rows of env i; `p`: the launch's tensors and configuration (ObsArgs, or a map set's SetObsArgs)
+template <int A, int M, int OT, bool WT, bool DUP, typename ARGS>
+__device__ __forceinline__ void obs_body(const LevelHdr &Lk, const RunCfg &R, const ARGS &p) {
   using Out = RowsT<WT ? AUX_WT : 0>;
-  OC_HDR_LOAD(p);
+  const Hdr L {Lk};
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
   constexpr int WS = state_words<A, M, DUP>();
@@ -1689,11 +1709,16 @@ __global__ void __launch_bounds__(256) k_obs(const ObsArgs p) {
   const int c0 = p.comm[i], c1 = p.comm[p.n + i];
   const bool ego_blind = p.cfg.blind_mask & 1;
   const Out ob(p.obs, p.n, 2 * F, i, OT == 1 ? 1 : 4);
-  const ObsSlots slots(p.R, false);
+  const ObsSlots slots(R, false);
 #pragma unroll
   for (int v = 0; v < 2; v++)
-    env_obs<A, M, DUP, OT>(L, p.R, slots, e, v, p.cfg.fow_radius, (p.cfg.blind_mask >> v) & 1, ego_blind, C, c0, c1, ob, v * F);
-  Out(p.timestep, p.n, 1, i, 8).st_f64(0, timestep_of(e.t, p.R));  // overcooked_env.py:146
+    env_obs<A, M, DUP, OT>(L, R, slots, e, v, p.cfg.fow_radius, (p.cfg.blind_mask >> v) & 1, ego_blind, C, c0, c1, ob, v * F);
+  Out(p.timestep, p.n, 1, i, 8).st_f64(0, timestep_of(e.t, R));  // overcooked_env.py:146
+}
+
+template <int A, int M, int OT, bool WT, bool DUP>
+__global__ void __launch_bounds__(256) k_obs(const ObsArgs p) {
+  obs_body<A, M, OT, WT, DUP>(p.L, p.R, p);
 }
 
 struct ImageArgs {
@@ -1809,21 +1834,28 @@ struct ResetArgs {
   int64_t n;
 };
 
-// OvercookedEnvironment.reset() (overcooked_environment.py:180-206), masked
-template <int A, int M, bool DUP>
-__global__ void __launch_bounds__(256) k_reset(const ResetArgs p) {
-  OC_HDR_LOAD(p);
+// OvercookedEnvironment.reset() (overcooked_environment.py:180-206), masked; `p`: the launch's tensors
+// (ResetArgs, or a map set's SetResetArgs)
+template <int A, int M, bool DUP, typename ARGS>
+__device__ __forceinline__ void reset_body(const LevelHdr &Lk, const void *const &tables, const int32_t &n16,
+                                           const ARGS &p) {
+  const Hdr L {Lk};
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
   if (p.mask != nullptr && p.mask[i] == 0) return;
   constexpr int WS = state_words<A, M, DUP>();
-  const Tables tb = stage_tables<false>(p.tables, p.n16, p.quot_bytes);
+  const Tables tb = stage_tables<false>(tables, n16, 0);
   int32_t w[WS];
 #pragma unroll
   for (int r = 0; r < WS; r++) w[r] = L.init_words(r);
   place_items<A, M, WS>(L, tb, p.placement, p.rng, p.n, i, w);
 #pragma unroll
   for (int r = 0; r < WS; r++) p.state[(int64_t)r * p.n + i] = w[r];
+}
+
+template <int A, int M, bool DUP>
+__global__ void __launch_bounds__(256) k_reset(const ResetArgs p) {
+  reset_body<A, M, DUP>(p.L, p.tables, p.n16, p);
 }
 
 // Uniform random (move, comm) indices of one player (include/oc_hip.h: oc_random_actions)
@@ -1921,11 +1953,12 @@ __device__ __forceinline__ float *pol_lds_ts() {
 // four duty waves and one barrier but covers 64 / LN envs; every lane runs its env's step up to
 // done/reward (the parts of an env compute identical values), an observation wave's parts then
 // store different rows, and the state and shaping waves work in part 0 alone.
-template <int M, bool LDS, int OT, bool WT, bool DUP, int XO, int DUTY, bool SPLIT, bool POL = false, int LN = 1>
+template <int M, bool LDS, int OT, bool WT, bool DUP, int XO, int DUTY, bool SPLIT, bool POL = false, int LN = 1,
+          typename ARGS = MultiArgs, typename MAPS = LaunchMap>
 __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int32_t *const actions_,
                                                 int32_t *const comm_, int64_t *const metrics_,
                                                 const int32_t n_, const int32_t block_, const void *const ego_src_,
-                                                const void *const alt_src_, const MultiArgs &p) {
+                                                const void *const alt_src_, const ARGS &p, const MAPS &maps) {
   constexpr int A = 2;
   constexpr bool D_STATE = (DUTY & DUTY_STATE) != 0, D_SHAPE = (DUTY & DUTY_SHAPE) != 0;
   using Out = RowsT<WT ? AUX_WT : 0>;
@@ -1934,7 +1967,6 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
 #else
   constexpr int POL_ROWS = 1;
 #endif
-  OC_HDR_LOAD(p);
   // n < 2^31 / (4 * rows): fits_buffer().  Split: one workgroup = SP waves over the same 64 envs.
   static_assert(LN == 1 || (SPLIT && XO == 0 && !POL && !LDS && DUTY != DUTY_ALL), "lane-split: the plain four-way split only");
   constexpr int EPW = 64 / LN;   // envs per split workgroup
@@ -1954,7 +1986,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
   // base pointers are formed AFTER the state loads are issued -- formed first, their scalar
   // kernarg load was waited for before a single vector load had left.
   Tables tb;
-  if constexpr (LDS) tb = stage_tables<true>(p.tables, p.n16, p.quot_bytes);
+  if constexpr (LDS) tb = stage_tables<true>(maps.ref().tables, maps.ref().n16, p.quot_bytes);
   MetricsSlot slot(metrics_, i);
   int reward = 0, done = 0, success = 0, comp = 0;
   bool err = false;
@@ -2030,12 +2062,15 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
       er.x = ac.ld(0), er.y = ac.ld(1);
       ar.x = ac.ld(2), ar.y = ac.ld(3);
     }
-    if constexpr (!LDS) tb = stage_tables<false>(p.tables, p.n16, p.quot_bytes);
+    // the env's map: the launch's, or (map sets) the group's record, looked up only now
+    const MapRef mp = maps.ref_behind_loads();
+    const Hdr L {mp.L};
+    if constexpr (!LDS) tb = stage_tables<false>(mp.tables, mp.n16, 0);   // (quot_bytes: 0 since v12, and unread here)
     // the output pointers are needed hundreds of instructions from here, where the compiler
     // would place their scalar loads -- and a wait on them -- in the middle of the step; fetch
     // them now, under the wait for the state that has to be served anyway
     asm volatile("" ::"s"(tb.dist), "s"(p.obs), "s"(p.timestep), "s"(p.reward), "s"(p.done),
-                 "s"(p.sparse), "s"(p.auto_reset), "s"(p.R.inv_T), "s"(p.R.inv_max_path));
+                 "s"(p.sparse), "s"(p.auto_reset), "s"(mp.R.inv_T), "s"(mp.R.inv_max_path));
     if constexpr (XO != 0) asm volatile("" ::"s"(p.opt.ep_return), "s"(p.opt.ep_length));
 #if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
     // structure library: the map's geometry is a kernel argument; the first things the step
@@ -2083,7 +2118,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
 #else
     constexpr int NPRE = 0;   // (the number of subtask rows is a run-time value)
 #endif
-    const ObsSlots slots(p.R, NPRE != 0);
+    const ObsSlots slots(mp.R, NPRE != 0);
     const RowsPreT<WT ? AUX_WT : 0, NPRE> obp(ob, DUTY == DUTY_OBS1 ? F : 0);
     if constexpr (NPRE != 0) asm volatile("" ::"s"(ob.rsrc));   // (the descriptor's words as well)
 #ifdef OC_SPECIALIZED
@@ -2176,7 +2211,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     ShapeIn<2> sin;
     ShapeLoads<2> sld;
     // (the plain variant is only launched for play == 0; the general one reads the flag)
-    env_step<A, M, DUP, XO == 2 ? 2 : 0, SPLIT>(L, p.R, tb.dist, tb.probe, e, act, reward, done, done_p, success, sin, sld OC_STAMP_PASS);
+    env_step<A, M, DUP, XO == 2 ? 2 : 0, SPLIT>(L, mp.R, tb.dist, tb.probe, e, act, reward, done, done_p, success, sin, sld OC_STAMP_PASS);
     comp = e.completed;
     err = e.err != err_before;
     if constexpr (D_STATE) {
@@ -2233,24 +2268,24 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     // arithmetic.  (It used to follow the last row store of viewer 0's arm, the longest.)
     constexpr bool TS_MINE = OBS_ONLY ? DUTY == TS_DUTY : (DUTY & DUTY_OBS0) != 0;
     [[maybe_unused]] double tsd = 0.0;
-    if constexpr (TS_MINE && OBS_ONLY && !POL) tsd = timestep_of(e.t, p.R);
+    if constexpr (TS_MINE && OBS_ONLY && !POL) tsd = timestep_of(e.t, mp.R);
     if constexpr (TS_MINE && OBS_ONLY && !POL) tso.st_f64(0, tsd);
     ShapeQ<2> sq;
-    if constexpr (D_SHAPE) shaping_lookup<2>(L, p.R.inv_max_path, sin, sld, sq OC_STAMP_PASS);
+    if constexpr (D_SHAPE) shaping_lookup<2>(L, mp.R.inv_max_path, sin, sld, sq OC_STAMP_PASS);
     const bool ego_blind = cfg_blind & 1;
     if constexpr (POL && SPLIT) {
       // (split launch with the policies fused: the rows also go to the LDS image the policy passes read)
       const int ln = (int)threadIdx.x & 63;
       if constexpr ((DUTY & DUTY_OBS0) != 0) {
         const RowsLdsT<WT ? AUX_WT : 0, OT> obl(ob, pol_lds_feat<POL_ROWS>(), 0, ln);
-        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obl, 0);
-        const double tsd = timestep_of(e.t, p.R);   // (formed in place: held across the rows it costs registers)
+        env_obs<A, M, DUP, OT>(L, mp.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obl, 0);
+        const double tsd = timestep_of(e.t, mp.R);   // (formed in place: held across the rows it costs registers)
         Out(p.timestep, p.n, 1, i, 8).st_f64(0, tsd);
         pol_lds_ts()[ln] = (float)tsd;
       }
       if constexpr ((DUTY & DUTY_OBS1) != 0) {
         const RowsLdsT<WT ? AUX_WT : 0, OT> obl(ob, pol_lds_feat<POL_ROWS>() + POL_ROWS * 64, F, ln);
-        env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obl, F);
+        env_obs<A, M, DUP, OT>(L, mp.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obl, F);
       }
     } else {
       // (obp: the rows with this wave's offsets pre-formed, or plain rows where none were)
@@ -2262,12 +2297,12 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
 #endif
       {
         if constexpr ((DUTY & DUTY_OBS0) != 0)
-          env_obs<A, M, DUP, OT>(L, p.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obp, 0);
+          env_obs<A, M, DUP, OT>(L, mp.R, slots, e, 0, p.cfg.obs.fow_radius, cfg_blind & 1, ego_blind, C, c0, c1, obp, 0);
         if constexpr ((DUTY & DUTY_OBS1) != 0)
-          env_obs<A, M, DUP, OT>(L, p.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obp, F);
+          env_obs<A, M, DUP, OT>(L, mp.R, slots, e, 1, p.cfg.obs.fow_radius, (cfg_blind >> 1) & 1, ego_blind, C, c0, c1, obp, F);
       }
       // (a wave that does more than one viewer's rows: behind them, or the value would be held across both)
-      if constexpr (TS_MINE && !OBS_ONLY) tso.st_f64(0, timestep_of(e.t, p.R));
+      if constexpr (TS_MINE && !OBS_ONLY) tso.st_f64(0, timestep_of(e.t, mp.R));
     }
     OC_STAMP(5);   // observation stores issued
     if constexpr (D_SHAPE) {
@@ -2292,6 +2327,7 @@ __device__ __forceinline__ void multi_step_body(int32_t *const state_, const int
     if constexpr (SPLIT) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int lane = (int)threadIdx.x & 63;
+    const Hdr L {maps.ref().L};
     const int C = p.cfg.obs.num_comm, F = 22 + L.S() + 2 * C;
     const uint32_t n32 = (uint32_t)n_;
     constexpr int ELEM = OT == 1 ? 1 : 4;
@@ -2363,9 +2399,10 @@ __global__ void __launch_bounds__(256) k_multi_step(int32_t *const state_, const
   [[maybe_unused]] const MultiArgs &pk = *reinterpret_cast<const MultiArgs *>(
       reinterpret_cast<const char *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(KernArgs, p));
 #endif
-#define OC_BODY(duty) multi_step_body<M, LDS, OT, WT, DUP, XO, (duty), true, POL, LN>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, pk)
+#define OC_BODY(duty) multi_step_body<M, LDS, OT, WT, DUP, XO, (duty), true, POL, LN>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, pk, LaunchMap{{pk.L, pk.R, pk.tables, pk.n16}})
   if constexpr (SP == 1) {
-    multi_step_body<M, LDS, OT, WT, DUP, XO, DUTY_ALL, false, POL>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, p);
+    multi_step_body<M, LDS, OT, WT, DUP, XO, DUTY_ALL, false, POL>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, p,
+                                                                   LaunchMap{{p.L, p.R, p.tables, p.n16}});
   } else {
     const int role = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     if constexpr (SP == 2) {   // two waves per 64 envs: state + viewer 0 | shaping + viewer 1
@@ -2386,5 +2423,140 @@ __global__ void __launch_bounds__(256) k_multi_step(int32_t *const state_, const
 #undef OC_BODY
   OC_TL_END(p.timeline, p.timeline_stride, LN);
 }
+
+
+// ---------------------------------------------------------------------------
+// map sets: envs on different maps of one structure in one launch
+// ---------------------------------------------------------------------------
+// Structure libraries only.  A map set is K maps of the library's structure and an assignment of
+// every GROUP of 64 envs (64 g ... 64 g + 63) to one of them: group_map[g].  Nothing in the step needs
+// a launch to share a map -- the geometry is a per-wave uniform value, read through the header's
+// accessors -- so the kernels below are the single-level code (multi_step_body, obs_body, reset_body)
+// handed the GROUP's header, run configuration and tables instead of the launch's:
+//   - one device allocation holds the K records (MapRecord) and, behind them, the maps' table images;
+//   - a workgroup always covers exactly one group (64 threads, or four duty waves over the same 64
+//     envs), so its map is group_map[blockIdx.x]: one scalar load, then the record's words through
+//     the CONSTANT address space -- scalar loads the compiler knows to be invariant, fetched where the
+//     code first needs them (the first use is the pin behind the state and action loads: those are
+//     issued from preloaded arguments and never wait for the record);
+//   - state, observation rows, outputs and the metrics slots (one per wave of 64 envs = per group)
+//     keep their layouts, so a map's counters are the sum of its groups' slots.
+#if defined(OC_SPECIALIZED) && !defined(OC_SPEC_GEOMETRY)
+struct MapRecord {
+  LevelHdr L;        // (only the GEOMETRY fields are ever read: the structure is folded into the code)
+  RunCfg R;          // inv_max_path is the map's; T and the ALLERGIC flags may differ as well
+  int64_t tab_off;   // the map's table image (oc_level_host.h: build_tables): bytes from the first record,
+  int32_t n16;       //   its size / 16
+  int32_t pad_;
+  const void *tables;   //   and its device address (the allocation's base + tab_off)
+};
+
+// the record of workgroup g's map, as seen through the constant address space
+__device__ __forceinline__ const MapRecord &group_record(const MapRecord *maps, const int32_t *group_map, unsigned g) {
+  typedef const __attribute__((address_space(4))) int32_t *ConstI32;
+  typedef const __attribute__((address_space(4))) MapRecord *ConstRec;
+  const int m = *((ConstI32)group_map + g);
+  return *(const MapRecord *)((ConstRec)maps + m);
+}
+// The fused step's source of its map.  The lookup is two dependent scalar loads (group_map[g], then
+// the record's words) behind the kernel arguments' own; it is ordered BEHIND the step's state and
+// action loads -- a scheduling barrier, and the pointers passed through a statement the compiler
+// cannot move -- so that the round trips run under the wait for the state.  (Left to the scheduler,
+// the chain and its three waits went in front of the first vector load.)
+struct GroupMap {
+  const MapRecord *maps;
+  const int32_t *group_map;
+  __device__ __forceinline__ MapRef ref_behind_loads() const {
+    __builtin_amdgcn_sched_barrier(0);
+    const MapRecord *ms = maps;
+    const int32_t *gm = group_map;
+    asm volatile("" : "+s"(ms), "+s"(gm));
+    const MapRecord &rec = group_record(ms, gm, blockIdx.x);
+    // What the step pins under the wait for the state (multi_step_body) is fetched HERE, and the region
+    // is closed: the scheduler otherwise moves the first arithmetic on loaded words -- and its wait for
+    // the state -- in front of the record's loads, which then start a round trip of their own.
+    asm volatile("" ::"s"(rec.tables), "s"(rec.R.inv_T), "s"(rec.R.inv_max_path), "s"(rec.L.W), "s"(rec.L.ncells),
+                 "s"(rec.L.max_path), "s"(rec.L.cell_lo[0]), "s"(rec.L.cell_hi[0]), "s"(rec.L.deliv_pos[0]));
+    __builtin_amdgcn_sched_barrier(0);
+    return MapRef{rec.L, rec.R, rec.tables, rec.n16};
+  }
+};
+
+struct SetMultiArgs {   // MultiArgs without the launch's map and without the fused policies
+  const MapRecord *maps;
+  const int32_t *group_map;
+  void *obs;
+  double *timestep;
+  double *reward;
+  int32_t *done;
+  int32_t *sparse;
+  const int32_t *placement;
+  uint32_t *rng;
+  oc_step_opts opt;
+  int64_t n;
+  int32_t auto_reset;
+  oc_wrap_cfg cfg;
+};
+
+// The fused 2-agent step of a map set: XO = 0 / 1, one wave or four duty waves per 64 envs (SP = 1 /
+// 4), write-through stores, tables in global memory.  Same leading (preloaded) scalars as
+// k_multi_step; block_'s low half is always 64.
+template <int M, int OT, bool DUP, int XO, int SP>
+__global__ void __launch_bounds__(256) k_mapset_step(int32_t *const state_, const int32_t *const actions_,
+                                                     int32_t *const comm_, int64_t *const metrics_,
+                                                     const int32_t n_, const int32_t block_,
+                                                     const void *const ego_src_, const void *const alt_src_,
+                                                     const SetMultiArgs p) {
+  static_assert(SP == 1 || SP == 4, "waves per 64 envs");
+  static_assert(XO == 0 || XO == 1, "the wrapper's standard configuration");
+  const GroupMap maps{p.maps, p.group_map};
+#define OC_BODY(duty, split) multi_step_body<M, false, OT, true, DUP, XO, (duty), (split), false, 1>(state_, actions_, comm_, metrics_, n_, block_, ego_src_, alt_src_, p, maps)
+  if constexpr (SP == 1) {
+    OC_BODY(DUTY_ALL, false);
+  } else {
+    const int role = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // (the order: see k_multi_step)
+    if (role == 0) OC_BODY(DUTY_OBS0, true);
+    else if (role == 1) OC_BODY(DUTY_OBS1, true);
+    else if (role == 2) OC_BODY(DUTY_STATE, true);
+    else OC_BODY(DUTY_SHAPE, true);
+  }
+#undef OC_BODY
+}
+
+struct SetObsArgs {
+  const MapRecord *maps;
+  const int32_t *group_map;
+  const int32_t *state;
+  const int32_t *comm;
+  void *obs;
+  double *timestep;
+  int64_t n;
+  oc_obs_cfg cfg;
+};
+
+// oc_obs for a map set (the rows after a reset); 64 threads per workgroup
+template <int M, int OT, bool DUP>
+__global__ void __launch_bounds__(64) k_mapset_obs(const SetObsArgs p) {
+  const MapRecord &rec = group_record(p.maps, p.group_map, blockIdx.x);
+  obs_body<2, M, OT, true, DUP>(rec.L, rec.R, p);
+}
+
+struct SetResetArgs {
+  const MapRecord *maps;
+  const int32_t *group_map;
+  int32_t *state;
+  const int32_t *mask;
+  const int32_t *placement;
+  uint32_t *rng;
+  int64_t n;
+};
+
+// oc_reset for a map set; 64 threads per workgroup
+template <int M, bool DUP>
+__global__ void __launch_bounds__(64) k_mapset_reset(const SetResetArgs p) {
+  const MapRecord &rec = group_record(p.maps, p.group_map, blockIdx.x);
+  reset_body<2, M, DUP>(rec.L, rec.tables, rec.n16, p);
+}
+#endif
 
 }  // namespace

@@ -107,10 +107,10 @@ class ClosedLoop:
         pt = venv.partner
         can = (isinstance(ego, FusedMLPPartner) and isinstance(pt, FusedMLPPartner) and pt.F == ego.F
                and pt.C == ego.C and ego.C <= 4 and venv._b.kernel_flavour == "spec"
-               and venv._b.standard_wrapper_config)
+               and venv._b.standard_wrapper_config and not venv._b.levels)     # (a map set has no fused policies)
         if one_launch and not can:
-            raise ValueError("one_launch needs two FusedMLPPartner of one shape, C <= 4, a specialised library "
-                             "and the wrapper's standard configuration")
+            raise ValueError("one_launch needs two FusedMLPPartner of one shape, C <= 4, a specialised library, "
+                             "the wrapper's standard configuration and a single level (no map set)")
         self.one_launch = (can and venv._b.launch_waves(general=True) == 4) if one_launch is None else bool(one_launch)
         self._primed = False
         self.prime()
@@ -185,16 +185,34 @@ class ClosedLoop:
         return v._obs_tensors(0), v._b.shaped_reward, v._b.done
 
 
+class _MapOf:
+    """A map set's batch as the per-env view sees it: ``level`` is the env's own map, the rest the batch's."""
+
+    def __init__(self, batch, level):
+        self._batch, self.level = batch, level
+
+    def __getattr__(self, name):
+        return getattr(self._batch, name)
+
+
 class OvercookedVecEnv(_VecEnvBase):
     def __init__(self, arglist, num_envs, partner=None, device="cuda", terminal_obs=False,
                  ego_agent_idx=0, subtask_order=None, level_dir=None, seed=0,
-                 track_episode_stats=True, use_graph=False, reuse_host_buffers=False, **batched_kw):
+                 track_episode_stats=True, use_graph=False, reuse_host_buffers=False, levels=None,
+                 group_map=None, envs_per_map=None, **batched_kw):
+        """``levels``: a list of level names / compiled levels of ONE structure -- the envs then live on
+        different maps (``BatchedOvercooked.from_maps``; ``group_map`` / ``envs_per_map`` assign them in
+        groups of 64, round-robin by default) and ``arglist.level`` is not looked at."""
         if _arg(arglist, "num_agents") != 2:
             raise ValueError("the gym_comm wrapper drives exactly 2 agents")
         self.arglist = arglist
         self.terminal_obs = bool(terminal_obs)
         self.track_episode_stats = bool(track_episode_stats)
-        self._b = BatchedOvercooked(
+        if levels is None and (group_map is not None or envs_per_map is not None):
+            raise ValueError("group_map / envs_per_map belong to levels=[...]")
+        make = BatchedOvercooked if levels is None else \
+            (lambda level, **kw: BatchedOvercooked.from_maps(levels, group_map=group_map, envs_per_map=envs_per_map, **kw))
+        self._b = make(
             _arg(arglist, "level"), num_agents=2, num_envs=num_envs,
             max_num_timesteps=_arg(arglist, "max_num_timesteps", 100),
             max_num_subtasks=_arg(arglist, "max_num_subtasks", 14),
@@ -560,7 +578,8 @@ class OvercookedVecEnv(_VecEnvBase):
         i = self._indices([i])[0]
         ent = self._env_views.get(i)
         if ent is None:
-            ent = [OvercookedEnvironment(self.arglist, _batch=self._b, _index=i, _view=True), -1]
+            b = _MapOf(self._b, self._b.level_of(i)) if self._b.levels else self._b      # env i on its own map
+            ent = [OvercookedEnvironment(self.arglist, _batch=b, _index=i, _view=True), -1]
             self._env_views[i] = ent
         if ent[1] != self._version:
             ent[0].mark_dirty()

@@ -285,6 +285,46 @@ OC_API int32_t oc_multi_step_waves(int64_t n, int32_t hint, int32_t general_vari
  * duty split.  OC_LAUNCH=lanes=... overrides the policy, never the results.  Host only. */
 OC_API int32_t oc_multi_step_lanes(int64_t n, int32_t hint, int32_t general_variant);
 
+/* ---- map sets: envs on different maps of one structure in one launch ------------------------
+ * A structure library (oc_is_specialized() == 1) keeps the map a run-time value, and a workgroup of
+ * the step always covers 64 envs, so one launch can step envs that live on DIFFERENT maps of the
+ * library's structure.  A map set is K >= 1 compiled levels with the same structure (recipes, item
+ * multiset, 2 agents, border kind) and the same subtask order; `group_map` -- a DEVICE pointer,
+ * int32 [ceil(n / 64)], values 0..K-1 -- says which map the envs 64 g ... 64 g + 63 live on.  The
+ * assignment belongs to the caller's batch and must not change while episodes run; the library
+ * never reads it on the host, so its values are the caller's to validate.  State, observation rows,
+ * every output and the metrics slots (one per group) keep the layouts above: a map's counters are
+ * the sum of its groups' slots.  No reference analogue (its env is one level per process).
+ *   oc_mapset_create   uploads the K maps (HOST blobs) to the current device.  Refuses -- OC_E_BADARG,
+ *       oc_last_error() names the offending blob's index -- a level library or the generic library,
+ *       k < 1, a blob whose structure differs from the library's or from blob 0's, a subtask order
+ *       or `play` flag that differs from blob 0's, and anything but 2 agents.
+ *   oc_mapset_reset / oc_mapset_obs / oc_mapset_multi_step   the single-level entry points with the
+ *       set and `group_map` in the level's place: the same arguments, checks, layouts and results
+ *       env by env (each env exactly as on its own map's oc_level_t), asynchronous on `stream`,
+ *       nothing allocated.  The fused step runs the wrapper's standard configuration (what
+ *       oc_multi_step folds: communication on, not ego-led, both CAN_MOVE, ego_agent_idx 0, nobody
+ *       BLIND, play off) with or without oc_step_opts' action sources and episode statistics, on
+ *       one wave or on four waves per 64 envs, with write-through stores; opts.policy is refused,
+ *       and a launch hint the set kernels have no variant for (two waves per 64 envs, OC_LAUNCH's
+ *       lanes / lds / wt / block) gets the nearest one they have.
+ *   oc_mapset_multi_step_waves   the waves per 64 envs oc_mapset_multi_step WILL LAUNCH: 1 or 4
+ *       (0 in a library without the set kernels).  Host only. */
+typedef struct oc_mapset oc_mapset_t;
+OC_API int oc_mapset_create(const int32_t *const *blobs, const int32_t *n_words, int32_t k, oc_mapset_t **out);
+OC_API int oc_mapset_destroy(oc_mapset_t *ms);
+OC_API int oc_mapset_reset(const oc_mapset_t *ms, const int32_t *group_map, int32_t *state, const int32_t *mask,
+                           const int32_t *placement, uint32_t *rng, int64_t n, void *stream);
+OC_API int oc_mapset_obs(const oc_mapset_t *ms, const int32_t *group_map, const int32_t *state,
+                         const int32_t *comm, const oc_obs_cfg *cfg, void *obs, double *timestep, int64_t n,
+                         void *stream);
+OC_API int oc_mapset_multi_step(const oc_mapset_t *ms, const int32_t *group_map, int32_t *state, int32_t *comm,
+                                const int32_t *actions, const oc_wrap_cfg *cfg, void *obs, double *timestep,
+                                double *reward, int32_t *done, int32_t *sparse, int32_t auto_reset,
+                                int64_t *metrics, const int32_t *placement, uint32_t *rng,
+                                const oc_step_opts *opts, int64_t n, void *stream);
+OC_API int32_t oc_mapset_multi_step_waves(int64_t n, int32_t hint, int32_t general_variant);
+
 /* Measurement hook of the TIMELINE build flavour (the same source compiled with -DOC_TIMELINE=1;
  * gym-comm_amd/specialize.py, variant="timeline"; every other build returns OC_E_BADARG).  In such a
  * build every wave of the step kernels reads the chip-wide constant-rate counter (s_memrealtime,
