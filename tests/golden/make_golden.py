@@ -234,7 +234,7 @@ def flat_obs(o):
     return ts, vec, tags
 
 
-def run_wrapper(name, level, T, steps, seed, kind="purpose", ego_agent_idx=0, **cfg):
+def run_wrapper(name, level, T, steps, seed, kind="purpose", ego_agent_idx=0, eps=0.15, **cfg):
     arg = H.make_arglist(level, 2, T, **cfg)
     env = H.wrapper_env(arg, ego_agent_idx=ego_agent_idx)
     base = env.base_env
@@ -247,7 +247,7 @@ def run_wrapper(name, level, T, steps, seed, kind="purpose", ego_agent_idx=0, **
                   ego_agent_idx=ego_agent_idx,
                   hashseed=os.environ.get("PYTHONHASHSEED", "unset"))
     rng = random.Random(seed)
-    pol = Purposeful(static["cells"], 2, rng, eps=0.15) if kind == "purpose" else None
+    pol = Purposeful(static["cells"], 2, rng, eps=eps) if kind == "purpose" else None
     rec = {k: [] for k in ("actions", "ts_bits", "obs", "rew_bits", "done", "reset_before", "pl_index")}
     placements = []
     # the constructor already did multi_reset(); record the obs of a fresh multi_reset
@@ -400,6 +400,103 @@ DUP_LEVELS = {
     "custom-three_tomatoes": "-t-t-t-\n/     -\n/     -\n*     -\n-     -\n-     p\n-----p-\n\nSimpleTomato\n\n2 1\n4 1\n4 4\n2 4",
 }
 
+def _rows(*rows):
+    return "\n".join(rows)
+
+
+_BIG_WIDE = ["-t------l-------", "/              -", "/     --       p", "*     --       p",
+             "-              -", "-      ----    -", "-              -", "----------------"]
+_BIG_TALL = ["-t----l-", "/      -", "/      -", "*      -", "-  --  -", "-      -", "-      -", "-  --  -",
+             "-      -", "-      -", "-      -", "- --   -", "-      -", "-      p", "-      p", "--------"]
+_BIG_ODD = ["-t---------l-", "/           -", "/   -----   -", "*           -", "-           -",
+            "-   --  --  -", "-           p", "-           p", "-------------"]
+
+_BIG_SQUARE = ["-t-------l-", "/         -", "/   ---   -", "*         -", "-         -", "-  --  -- -",
+               "-         -", "-         -", "-    --   p", "-         p", "-----------"]
+
+BIG_LEVELS = {
+    # maps above 64 cells (no shipped level is): both 64-bit words of the tile bit-planes, coordinates
+    # 11..15, W = 16 and an odd W, MAX_PATH 49 / 51 / 45, a distance table of up to 16 KB.  Closed
+    # border, at most 64 Counter tiles, agent starts on Floor
+    "custom-big_wide_salad": _rows(*_BIG_WIDE) + "\n\nSalad\n\n2 1\n13 6\n8 4\n4 6",
+    "custom-big_tall_salad": _rows(*_BIG_TALL) + "\n\nSalad\n\n2 1\n5 14\n3 8\n5 3",
+    "custom-big_odd_tomato": _rows(*_BIG_ODD) + "\n\nSimpleTomato\n\n2 1\n10 7\n6 4\n3 6",
+    # 11 x 11, the largest SQUARE map the library takes (121 cells): get_partial_observability_FOW
+    # allocates [plane][height][width] and indexes [plane][x][y] (overcooked_env.py:167,180), so the
+    # reference raises IndexError on every map that is not square
+    "custom-big_square_salad": _rows(*_BIG_SQUARE) + "\n\nSalad\n\n2 1\n8 9\n5 4\n3 7",
+    # the 16 x 8 map with a second tomato (dup mode's per-cell probe table for x above 10)
+    "custom-big_two_tomatoes": _rows("-t---t--l-------", *_BIG_WIDE[1:]) + "\n\nSimpleTomato\n\n2 1\n13 6\n8 4\n4 6",
+    # the 16 x 8 map in the shipped random-* files' style: no item on the map, a fourth block that
+    # scatters them over its 49 Counter tiles at every reset
+    "random-big_salad": _rows("----------------", "/              -", "/     --       -", "*     --       -",
+                                     *_BIG_WIDE[4:]) + "\n\nSalad\n\n2 1\n13 6\n8 4\n4 6\n\ntlpp",
+}
+
+
+# wrapper tapes on the big maps: file, level, T, steps, seed, wrapper settings
+WRAP_BIG = [
+    # (eps 0.04: with the default 0.15 -- and no no-op to fall back on -- no tape delivered a salad here)
+    ("cwrap_cbigwide_r3.npz", "custom-big_wide_salad", 300, 3000, 173,
+     {"fow_radius": 3, "num_communication": 3, "eps": 0.04}),
+    ("cwrap_cbigtall_r2.npz", "custom-big_tall_salad", 300, 3000, 176, {"eps": 0.04}),
+    ("cwrap_dup_big_two_tomatoes_r3.npz", "custom-big_two_tomatoes", 300, 3000, 171, {"fow_radius": 3, "eps": 0.04}),
+    ("rwrap_rbig_r3.npz", "random-big_salad", 300, 3000, 170, {"fow_radius": 3, "eps": 0.04}),
+]
+
+
+def _successes(done, T):
+    """Episodes that ended before the time limit (the wrapper's reward is shaped, so its sum says
+    nothing about deliveries)."""
+    ends = np.nonzero(done)[0]
+    return int((np.diff(np.concatenate([[-1], ends])) < T).sum())
+
+
+def main_big(summary):
+    """Maps above 64 cells (`--big-only`; `--match=TEXT` records only the files whose name holds TEXT)."""
+    H.use_custom_levels(BIG_LEVELS)
+    match = [a[len("--match="):] for a in sys.argv if a.startswith("--match=")]
+
+    def wanted(fn):
+        return all(m in fn for m in match)
+
+    def save(fn, out, level, info):
+        st = json.loads(str(out["static_json"]))
+        st["level_text"] = BIG_LEVELS[level]
+        out["static_json"] = np.array(json.dumps(st))
+        np.savez_compressed(os.path.join(HERE, fn), **out)
+        summary[fn] = info
+        print(fn, info, "%d bytes" % os.path.getsize(os.path.join(HERE, fn)), flush=True)
+
+    for fn, level, A, T, tapes in [
+            ("cbase_custom-big_wide_salad_a2.npz", "custom-big_wide_salad", 2, 200,
+             [("rand5", (300, 160)), ("purpose", (4000, 167))]),
+            ("cbase_custom-big_tall_salad_a3.npz", "custom-big_tall_salad", 3, 200, [("purpose", (3500, 162))]),
+            ("cbase_custom-big_odd_tomato_a4.npz", "custom-big_odd_tomato", 4, 150, [("purpose", (2500, 163))]),
+            ("cbase_dup_big_two_tomatoes_a2.npz", "custom-big_two_tomatoes", 2, 200, [("purpose", (4000, 164))]),
+            ("rbase_random-big_salad_a2.npz", "random-big_salad", 2, 150, [("purpose", (3500, 165))])]:
+        if not wanted(fn):
+            continue
+        random.seed(1002)
+        out, sr, nd = run_base(level, A, T, tapes)
+        info = {"steps": int(len(out["t"])), "sum_reward": sr, "episodes": nd}
+        if "_dup_" in fn:
+            info.update(steps_with_goal_count_above_1=int((out["goal_count"] > 1).any(axis=1).sum()),
+                        max_objects=int(out["nobj"].max()), min_objects=int(out["nobj"].min()))
+        save(fn, out, level, info)
+    for fn, level, T, steps, seed, kw in WRAP_BIG:
+        if not wanted(fn):
+            continue
+        random.seed(seed)
+        out, nd = run_wrapper(fn, level, T, steps, seed, **kw)
+        save(fn, out, level, {"steps": int(len(out["done"])), "episodes": nd,
+                              "successful_episodes": _successes(out["done"], T)})
+    fn, level = "fow_bigsquare_r3.npz", "custom-big_square_salad"
+    if wanted(fn):
+        out = run_fow(level, 150, 600, 174, 3)
+        save(fn, out, level, {"steps": int(len(out["actions"])), "completed_subtasks_sum": int(out["completed"].sum()),
+                              "episodes": int(out["reset_before"].sum())})
+
 
 def main_play(summary):
     """arglist.play = True: the "playable" branches of interact() (utils/interact.py:44-47,52,
@@ -539,6 +636,13 @@ def main():
         with open(os.path.join(HERE, "SUMMARY.json")) as f:
             summary = json.load(f)
         main_dup(summary, only3="--dup3-only" in sys.argv)
+        with open(os.path.join(HERE, "SUMMARY.json"), "w") as f:
+            json.dump(summary, f, indent=1, sort_keys=True)
+        return
+    if "--big-only" in sys.argv:
+        with open(os.path.join(HERE, "SUMMARY.json")) as f:
+            summary = json.load(f)
+        main_big(summary)
         with open(os.path.join(HERE, "SUMMARY.json"), "w") as f:
             json.dump(summary, f, indent=1, sort_keys=True)
         return

@@ -23,6 +23,11 @@ SPEC_GOLDEN = ["base_open-divider_tomato_a2.npz", "base_full-divider_salad_a2.np
                "cwrap_dup_two_tomatoes_small_r1.npz",
                # ... three times (the count == 3 paths: 2-bit goal counts at their maximum, five items)
                "cbase_dup_three_tomatoes_a2.npz", "cbase_dup_three_tomatoes_a3.npz", "cwrap_dup_three_tomatoes_r2.npz",
+               # maps above 64 cells (the planes128 = 1 instantiations), one that repeats a type, one that scatters
+               "cbase_custom-big_wide_salad_a2.npz", "cbase_custom-big_tall_salad_a3.npz",
+               "cbase_custom-big_odd_tomato_a4.npz", "cwrap_cbigwide_r3.npz", "cwrap_cbigtall_r2.npz",
+               "fow_bigsquare_r3.npz", "cbase_dup_big_two_tomatoes_a2.npz", "cwrap_dup_big_two_tomatoes_r3.npz",
+               "rbase_random-big_salad_a2.npz", "rwrap_rbig_r3.npz",
                # arglist.play = True (a run-time flag: the same libraries)
                "pbase_open-divider_tomato_a2.npz", "pbase_partial-divider_tl_a3.npz", "pwrap_play_salad_c3.npz"]
 
@@ -31,6 +36,9 @@ SPEC_GOLDEN = ["base_open-divider_tomato_a2.npz", "base_full-divider_salad_a2.np
 DUP_SEEDED = [("cbase_dup_two_tomatoes_small_a2.npz", 2), ("cbase_dup_two_tomatoes_small_a3.npz", 3),
               ("cbase_dup_two_lettuces_salad_a2.npz", 2), ("cbase_dup_two_tomatoes_a3.npz", 3),
               ("cbase_dup_three_tomatoes_a2.npz", 2), ("cbase_dup_three_tomatoes_a3.npz", 3)]
+
+# (map of tests/big_maps.py, agents) the seeded big-map tests step beyond what those fixtures compile
+BIG_SEEDED = [("odd_13x9", 2)]
 
 
 def all_spec_levels():
@@ -42,4 +50,6 @@ def all_spec_levels():
     for f, a in DUP_SEEDED:
         _, st = load_golden(os.path.join(GOLDEN, f))
         out.append(compiler.compile_level(levels.parse_level_text(st["level"], st["level_text"]), a, 90))
+    import big_maps
+    out += [big_maps.level(name, a) for name, a in BIG_SEEDED]
     return out

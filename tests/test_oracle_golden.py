@@ -19,7 +19,12 @@ def _pack(cells):
 
 
 def test_fixtures_present():
-    assert len(BASE) >= 10 and len(WRAP) >= 15
+    assert len(BASE) >= 38 and len(WRAP) >= 33 and len(golden_files("fow_")) >= 3
+    big = [p for p in BASE + WRAP + golden_files("fow_") if "big" in os.path.basename(p).replace("small_wide_big", "")]
+    assert len(big) == 10           # maps above 64 cells (make_golden.py --big-only)
+    for p in big:
+        st = load_golden(p)[1]
+        assert st["width"] * st["height"] > 64 and "level_text" in st, p
 
 
 @pytest.mark.parametrize("path", BASE, ids=[os.path.basename(p) for p in BASE])
