@@ -128,6 +128,11 @@ def _libs_table():
             "oc_hostio_last_error": (cstr, None),
             "oc_pack_host_bytes": (i64, [i32, i32, i32, i32, i32, i32, i32, i64]),
             "oc_pack_host": (cint, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+            # host-mapped I/O: the same pack for an `out` across PCIe, and the mapped allocation
+            "oc_pack_host_tiled": (cint, [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+            "oc_pack_host_tile": (cint, None),
+            "oc_hostio_alloc": (cint, [i64, P(vp), P(vp)]),
+            "oc_hostio_free": (cint, [vp]),
         }),
         "rollout": Lib("OC_ROLLOUT_LIB", "oc_rollout_abi_version", 1, "oc_rollout_last_error", {
             "oc_rollout_abi_version": (cint, None),

@@ -40,9 +40,13 @@ Partners
 Subclasses ``stable_baselines3.common.vec_env.VecEnv`` when SB3 is importable; otherwise a
 structural stand-in with the same methods.  ``step_tensors`` is the zero-copy variant for
 policies that live on the GPU; the numpy API packs a step's arrays with one launch of
-``oc_pack_host`` (include/oc_hostio.h) and one PCIe copy.
+``oc_pack_host`` (include/oc_hostio.h) and one PCIe copy -- or, with ``host_io="mapped"``, has
+the kernels read the actions from host-mapped memory and write the packed step into it, and
+finishes the step by polling an event (no copy, no blocking wait).
 """
+import ctypes
 import os
+import time
 import weakref
 
 import numpy as np
@@ -86,6 +90,36 @@ class ObsView(dict):
     (f64 [n]).  The same objects every step; the next step overwrites their contents."""
     rows = None
     timestep = None
+
+
+class MappedBuffer:
+    """``nbytes`` of pinned host memory that kernels read and write in place (include/oc_hostio.h:
+    ``oc_hostio_alloc``): ``dev`` is its address for kernels, ``view()`` a uint8 array over it for
+    the host.  The object is the ``base`` of that array and so of every array cut from it: the
+    memory is freed when the last of them and the last other reference to the object are gone.
+    Nothing here waits for a kernel that may still be writing it (an env dropped between
+    ``step_async`` and ``step_wait``): ``hipHostFree`` synchronises the device before it releases
+    the memory, and that is what this relies on."""
+
+    def __init__(self, L, dev_index, nbytes):
+        host, dev = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.call(L, "oc_hostio_alloc", dev_index, int(nbytes), ctypes.byref(host), ctypes.byref(dev), stream=False)
+        self._L, self.host, self.dev, self.nbytes = L, host.value, dev.value, int(nbytes)
+
+    @property
+    def __array_interface__(self):
+        return {"shape": (self.nbytes,), "typestr": "|u1", "data": (self.host, False), "version": 3}
+
+    def view(self):
+        return np.asarray(self)
+
+    def __del__(self):
+        host, self.host = getattr(self, "host", None), None
+        if host:
+            try:
+                self._L.oc_hostio_free(host)
+            except Exception:                   # interpreter shutdown
+                pass
 
 
 class ClosedLoop:
@@ -199,10 +233,18 @@ class OvercookedVecEnv(_VecEnvBase):
     def __init__(self, arglist, num_envs, partner=None, device="cuda", terminal_obs=False,
                  ego_agent_idx=0, subtask_order=None, level_dir=None, seed=0,
                  track_episode_stats=True, use_graph=False, reuse_host_buffers=False, levels=None,
-                 group_map=None, envs_per_map=None, **batched_kw):
+                 group_map=None, envs_per_map=None, host_io="copy", **batched_kw):
         """``levels``: a list of level names / compiled levels of ONE structure -- the envs then live on
         different maps (``BatchedOvercooked.from_maps``; ``group_map`` / ``envs_per_map`` assign them in
-        groups of 64, round-robin by default) and ``arglist.level`` is not looked at."""
+        groups of 64, round-robin by default) and ``arglist.level`` is not looked at.
+
+        ``host_io``: how the numpy API crosses PCIe.  ``"copy"``: staged copies in and out and a
+        blocking wait.  ``"mapped"``: the step kernel reads the actions from host-mapped memory,
+        ``oc_pack_host_tiled`` writes the packed step into one of two alternating host-mapped
+        buffers, ``step_async`` starts that work and ``step_wait`` polls for its end."""
+        if host_io not in ("copy", "mapped"):
+            raise ValueError("host_io must be \"copy\" or \"mapped\", not %r" % (host_io,))
+        self._host_io = host_io
         if _arg(arglist, "num_agents") != 2:
             raise ValueError("the gym_comm wrapper drives exactly 2 agents")
         self.arglist = arglist
@@ -248,9 +290,12 @@ class OvercookedVecEnv(_VecEnvBase):
         self._host_stats = None
         # numpy API: False = every step returns fresh arrays (a host copy out of the pinned
         # buffer); True = the arrays are views of two alternating pinned buffers, valid until
-        # the step after next (what a rollout collector that copies them on arrival needs)
+        # the step after next (what a rollout collector that copies them on arrival needs);
+        # host_io="mapped": the same of two host-mapped buffers (then the same array objects every other step)
         self._reuse_host = bool(reuse_host_buffers)
         self._host_flip = 0
+        self._act_mapped = None                          # host_io="mapped": the actions' MappedBuffer
+        self._inflight = None                            # ... and the step started by step_async
 
     @property
     def partner(self):
@@ -387,6 +432,14 @@ class OvercookedVecEnv(_VecEnvBase):
             self._ego_pairs = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self._b.device)
         return self._ego_pairs
 
+    def _fast_step(self, f, ego_ptr, pairs_int64):
+        """The single-launch step of ``_fast_plan()`` on the ego pairs at device address ``ego_ptr``
+        (None: the ego's rows of ``self._act``), and the bookkeeping of a step."""
+        f["launch"](ego_ptr, pairs_int64)
+        self._version += 1
+        self._last_terminal = None
+        return f["obs"], self._b.shaped_reward, self._b.done
+
     def step_tensors(self, ego_actions=None):
         """ego_actions: int tensor [n, 2] on the device (None: already written into
         ``ego_action_rows``).  A contiguous int32 or int64 tensor is handed to the kernel as it
@@ -409,10 +462,7 @@ class OvercookedVecEnv(_VecEnvBase):
                     ea = self._ego_pairs
                 ego_ptr = ea.data_ptr()
                 i64 = ea.dtype is torch.int64
-            f["launch"](ego_ptr, ego_ptr is not None and i64)
-            self._version += 1
-            self._last_terminal = None
-            return f["obs"], b.shaped_reward, b.done
+            return self._fast_step(f, ego_ptr, ego_ptr is not None and i64)
         ego_pairs = None
         if ego_actions is not None:
             ea = torch.as_tensor(ego_actions, device=b.device)
@@ -478,11 +528,18 @@ class OvercookedVecEnv(_VecEnvBase):
             off[name] = (o, o + nbytes)
             o += nbytes
         assert o == total
-        return {"L": L, "plan": torch.from_numpy(plan).to(b.device), "width": width, "cols": cols, "stats": stats,
-                "dev": torch.empty(max(total, 1), dtype=torch.uint8, device=b.device),
-                "pinned": [torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
-                           for _ in range(2 if self._reuse_host else 1)], "off": off,
-                "ot": OBS_TYPE[b.obs.dtype]}
+        hp = {"L": L, "plan": torch.from_numpy(plan).to(b.device), "width": width, "cols": cols, "stats": stats,
+              "off": off, "ot": OBS_TYPE[b.obs.dtype]}
+        if self._host_io == "mapped":
+            # two host-mapped buffers the pack kernel writes in turn, and the event that ends a step
+            hp["mapped"] = [MappedBuffer(L, b._dev_index, max(total, 1)) for _ in range(2)]
+            hp["event"] = torch.cuda.Event()
+            hp["views"] = [None, None]
+        else:
+            hp["dev"] = torch.empty(max(total, 1), dtype=torch.uint8, device=b.device)
+            hp["pinned"] = [torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
+                            for _ in range(2 if self._reuse_host else 1)]
+        return hp
 
     def _host_step(self, rew=None, done=None):
         """Everything the numpy API returns for one step: ONE launch (``oc_pack_host``,
@@ -504,6 +561,11 @@ class OvercookedVecEnv(_VecEnvBase):
         pinned.copy_(hp["dev"], non_blocking=True)
         torch.cuda.current_stream(b.device).synchronize()
         host = pinned.numpy() if self._reuse_host else pinned.numpy().copy()
+        return self._host_views(hp, host, rew, done)
+
+    def _host_views(self, hp, host, rew, done):
+        """The per-key arrays, rewards and done flags as views of one packed step ``host`` (uint8)."""
+        n = self.num_envs
         view = lambda name, dt, shape: host[hp["off"][name][0]:hp["off"][name][1]].view(dt).reshape(shape)
         blocks = (view("b64", np.int64, (n, hp["width"][0])), view("b32", np.float32, (n, hp["width"][1])),
                   view("b8", np.int8, (n, hp["width"][2])))
@@ -513,7 +575,47 @@ class OvercookedVecEnv(_VecEnvBase):
         return (obs, view("rew", np.float32, (n,)) if rew is not None else None,
                 view("done", np.int32, (n,)) if done is not None else None)
 
+    def _mapped_pack(self):
+        """host_io="mapped", first half: ``oc_pack_host_tiled`` straight into the next of the two
+        host-mapped buffers, and an event behind it."""
+        b = self._b
+        hp = self._host_plan_cache
+        if hp is None:
+            hp = self._host_plan_cache = self._host_plan()
+        dp = lambda t: None if t is None else t.data_ptr()
+        self._host_flip ^= 1
+        _lib.call(hp["L"], "oc_pack_host_tiled", b._dev_index, b.obs[0].data_ptr(), hp["ot"], b.F,
+                  hp["plan"].data_ptr(), hp["width"][0], hp["width"][1], hp["width"][2], b.timestep.data_ptr(),
+                  b.shaped_reward.data_ptr(), dp(b.ep_return), b.done.data_ptr(), dp(b.ep_length),
+                  hp["mapped"][self._host_flip].dev, self.num_envs)
+        hp["event"].record(torch.cuda.current_stream(b.device))
+
+    def _mapped_wait(self, rew=None, done=None, timeout=30.0):
+        """host_io="mapped", second half: poll the event (a blocked wait on this runtime can return
+        tens of milliseconds late), then the views of the buffer just written."""
+        hp = self._host_plan_cache
+        ev = hp["event"]
+        deadline = time.monotonic() + timeout
+        while not ev.query():
+            if time.monotonic() > deadline:
+                raise RuntimeError("host_io=\"mapped\": the step did not finish within %g s" % timeout)
+        host = hp["mapped"][self._host_flip].view()
+        if not self._reuse_host:
+            return self._host_views(hp, host.copy(), rew, done)
+        # views of the two buffers are the same arrays every other step: cut them once per buffer
+        cut = hp["views"][self._host_flip]
+        if cut is None:
+            cut = hp["views"][self._host_flip] = self._host_views(hp, host, True, True) + (self._host_stats,)
+        obs, rew_np, done_np, self._host_stats = cut
+        return dict(obs), rew_np if rew is not None else None, done_np if done is not None else None
+
     def _ego_obs_numpy(self):
+        if self._host_io == "mapped":
+            if self._inflight is not None:          # a step nobody waited for: let it end first
+                self._mapped_wait()
+                self._inflight = None
+            self._mapped_pack()
+            return self._mapped_wait()[0]
         return self._host_step()[0]
 
     def reset(self):
@@ -521,17 +623,50 @@ class OvercookedVecEnv(_VecEnvBase):
         return self._ego_obs_numpy()
 
     def step_async(self, actions):
+        if self._host_io == "mapped":
+            return self._mapped_step_async(actions)
         self._pending = np.asarray(actions)
 
-    def step_wait(self):
+    def _staged_actions(self, actions):
         # host actions -> pinned staging -> the device pairs the kernel consumes as they lie
         if self._act_pinned is None:
             self._act_pinned = torch.empty((self.num_envs, 2), dtype=torch.int32, pin_memory=True)
-        np.copyto(self._act_pinned.numpy(), self._pending.reshape(self.num_envs, 2), casting="unsafe")
+        np.copyto(self._act_pinned.numpy(), actions.reshape(self.num_envs, 2), casting="unsafe")
         ego_pairs = self._staged_pairs()
         ego_pairs.copy_(self._act_pinned, non_blocking=True)
-        _, rew, done = self.step_tensors(ego_pairs)
-        obs_np, rew_np, done_i32 = self._host_step(rew, done)
+        return ego_pairs
+
+    def _mapped_step_async(self, actions):
+        """host_io="mapped": everything of a step that can be started -- the actions into mapped
+        memory, the fused step, the pack into mapped memory, the event."""
+        if self._inflight is not None:
+            raise RuntimeError("step_async called again before step_wait")
+        b, n = self._b, self.num_envs
+        actions = np.asarray(actions)
+        f = self._fast
+        if f is None:
+            f = self._fast = self._fast_plan()
+        if f:
+            # the single-launch step reads the ego's pairs where the host wrote them: no staging copy
+            if self._act_mapped is None:
+                self._act_mapped = MappedBuffer(_lib.load(lib="hostio"), b._dev_index, n * 2 * 4)
+                self._act_mapped_np = self._act_mapped.view().view(np.int32).reshape(n, 2)
+            np.copyto(self._act_mapped_np, actions.reshape(n, 2), casting="unsafe")
+            _, rew, done = self._fast_step(f, self._act_mapped.dev, False)
+        else:
+            _, rew, done = self.step_tensors(self._staged_actions(actions))
+        self._mapped_pack()
+        self._inflight = (rew, done)
+
+    def step_wait(self):
+        if self._host_io == "mapped":
+            if self._inflight is None:
+                raise RuntimeError("step_wait without step_async")
+            (rew, done), self._inflight = self._inflight, None
+            obs_np, rew_np, done_i32 = self._mapped_wait(rew, done)
+        else:
+            _, rew, done = self.step_tensors(self._staged_actions(self._pending))
+            obs_np, rew_np, done_i32 = self._host_step(rew, done)
         done_np = done_i32.astype(bool)
         infos = self._infos                       # the same list every step (as DummyVecEnv's buf_infos)
         for i in self._dirty:
@@ -552,7 +687,9 @@ class OvercookedVecEnv(_VecEnvBase):
         return obs_np, rew_np, done_np, list(infos)   # shallow copy: holders keep their dicts
 
     def close(self):
-        pass
+        if self._inflight is not None:      # host_io="mapped": a step nobody waited for ends first
+            self._mapped_wait()
+            self._inflight = None
 
     def seed(self, seed=None):
         return [seed] * self.num_envs

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Throughput of the SB3-shaped boundary: tensor API (device-resident policy; eager launches
 and the one-hipGraph-replay variant), the ego-policy-in-the-graph closed loop, and the numpy
-API (host buffers in and out: the PCIe-inclusive rate quoted in DESIGN.md)."""
+API (host buffers in and out: the PCIe-inclusive rate quoted in DESIGN.md) -- with staged copies
+(``host_io="copy"``) and with host-mapped buffers (``host_io="mapped"``), the four rows twice,
+copy and mapped in turn, so that the spread between two passes shows next to the difference."""
 import os
 import sys
 import time
@@ -70,6 +72,24 @@ def main():
             print("n=%d numpy API (host actions in, 11 host obs arrays + infos out, PCIe-inclusive; %s): %.1f us/step, %.3g env-steps/s"
                   % (n, "views of two alternating pinned buffers" if reuse else "fresh arrays every step",
                      dt * 1e6, n / dt), flush=True)
+        for rnd in (1, 2):
+            for reuse in (False, True):
+                for host_io in ("copy", "mapped"):
+                    dt = numpy_rate(arg, n, acts_np, reuse, host_io)
+                    print("n=%d numpy API, pass %d, host_io=%-6s (%s): %.1f us/step, %.3g env-steps/s"
+                          % (n, rnd, host_io, "reused buffers" if reuse else "fresh arrays", dt * 1e6, n / dt), flush=True)
+
+
+def numpy_rate(arg, n, acts_np, reuse, host_io):
+    venv = OvercookedVecEnv(arg, n, seed=1, reuse_host_buffers=reuse, host_io=host_io)
+    venv.reset()
+    for k in range(10):
+        venv.step(acts_np[k % 64])
+    steps = 400 if n <= 4096 else 40
+    t0 = time.perf_counter()
+    for k in range(steps):
+        venv.step(acts_np[k % 64])
+    return (time.perf_counter() - t0) / steps
 
 
 if __name__ == "__main__":
