@@ -43,6 +43,19 @@ def obs_layout(S, C):
     return out
 
 
+def nominal_placement(levels, group_map, n):
+    """int32 [M][n]: every env's item start cells (x | y<<4, world order) as its OWN map compiled them --
+    the first Counters of that map for the scattered items.  ``levels``: the compiled maps of a set (one
+    for a single level); ``group_map``: a map index per group of 64 envs, or None for map 0 everywhere."""
+    cols = np.array([lv.pack_placement([(x, y) for _, x, y in lv.items]) for lv in levels], np.int32)
+    cols = cols.reshape(len(levels), -1)
+    if group_map is None:
+        env_map = np.zeros(int(n), np.int64)
+    else:
+        env_map = np.asarray(group_map, np.int64)[np.arange(int(n)) // 64]
+    return np.ascontiguousarray(cols[env_map].T)
+
+
 class BatchedOvercooked:
     def __init__(self, level, num_agents=2, num_envs=4096, max_num_timesteps=100,
                  ego_config=None, partner_config=None, num_communication=2,
@@ -160,9 +173,9 @@ class BatchedOvercooked:
             if placement_mode == "rng":
                 self.rng = pcg32_seed_states(seed, (n,), self.device)
             elif placement_mode == "host":
-                nominal = torch.tensor(lv.pack_placement([(x, y) for _, x, y in lv.items]),
-                                       dtype=torch.int32)
-                self.placement = nominal.view(-1, 1).repeat(1, n).contiguous().to(self.device)
+                # every env starts on its own map's nominal cells (a set's maps differ in their Counters)
+                nominal = nominal_placement(self.levels or [lv], self.group_map_host, n)
+                self.placement = torch.from_numpy(nominal).to(self.device)
             else:
                 raise ValueError("placement_mode must be 'rng' or 'host'")
         self.reset()

@@ -25,7 +25,8 @@ C headers, flags) -- built by ``__graft_entry__.build()`` (structure libraries f
 level, level libraries for the BASELINE configs and the tested levels) and travelling with the repo
 snapshot.  Measurement variants of a level library (``variant="timeline"``: -DOC_TIMELINE, bench.py
 --decompose) are never picked unless asked for.  max_num_timesteps, the ALLERGIC flags
-and the subtask order stay run-time arguments and select nothing.
+and the subtask order stay run-time arguments and select nothing -- but for the order of a level's
+Deliver subtasks among themselves (the tl levels have two), which the header's delivery tables keep.
 """
 import ctypes
 import hashlib

@@ -96,21 +96,42 @@ class SetOracle:
                 out[k][ix] = v
         return out
 
-    def multi_step(self, acts):
+    def set_placement(self, cells):
+        """[M][n] packed start cells in the batch's env order; every map's oracle gets its own envs' columns."""
+        for m, o, ix in self._each():
+            o.set_placement(np.ascontiguousarray(np.asarray(cells)[:, ix]))
+
+    def multi_step(self, acts, auto_reset=True):
         n, F = self.n, 22 + self.S + 2 * C
         r = {"obs": np.zeros((2, F, n), np.int32), "timestep": np.zeros(n), "reward": np.zeros(n),
              "done": np.zeros(n, np.int32), "comm": np.zeros((2, n), np.int32), "sparse": np.zeros(n, np.int32),
-             "per_map": []}
+             "raised": np.zeros(n, np.int32), "success": np.zeros(n, np.int32), "per_map": []}
         for m, o, ix in self._each():
             obs, ts, rew, done = o.multi_step(np.ascontiguousarray(acts[:, ix]), self.comm[m], RADIUS, 0, C,
-                                              auto_reset=True)
+                                              auto_reset=auto_reset)
             last = o.last_step()
             r["obs"][:, :, ix], r["timestep"][ix], r["reward"][ix], r["done"][ix] = obs, ts, rew, done
             r["comm"][:, ix], r["sparse"][ix] = self.comm[m], last["sparse"]
+            r["raised"][ix], r["success"][ix] = last["raised"], last["success"]
             r["per_map"].append((m, {"env_steps": len(ix), "episodes": int(done.sum()),
                                      "successes": int(last["success"].sum()), "reward_sum": int(last["sparse"].sum()),
                                      "completed_subtasks_sum": int(last["completed"].sum()),
                                      "errors": int(last["raised"].sum())}))
+        r["snapshot"] = self.snapshot()
+        return r
+
+    def replace_finished(self, r, cells):
+        """After ``multi_step(acts, auto_reset=False)``: the envs that finished start their next episode on
+        ``cells`` ([M][n]: a placement nobody can know ahead, such as the library's own draw) -- a masked
+        reset -- and their rows and timestep in ``r`` become that episode's first observation."""
+        self.set_placement(cells)
+        self.reset(r["done"])
+        for m, o, ix in self._each():
+            for j, i in enumerate(ix):
+                if r["done"][i]:
+                    for v in range(2):
+                        r["obs"][v, :, i], r["timestep"][i] = o.obs(j, v, RADIUS, False, False, C,
+                                                                    [int(self.comm[m][0, j]), int(self.comm[m][1, j])])
         r["snapshot"] = self.snapshot()
         return r
 
