@@ -775,6 +775,15 @@ OC_EXPORT void oc_oracle_debug_set(void *h, const int32_t *agents, const int32_t
   }
 }
 
+/* TEST ONLY: start (or continue) the episode at step counter t, every other field as it is: what t
+ * all-stay steps from here would leave when nothing else moves.  The counter is a plain int
+ * here and does not saturate (the kernels keep 16 bits of it, include/oc_level.h). */
+OC_EXPORT void oc_oracle_debug_set_t(void *h, int32_t t) { ((Env *)h)->t = t; }
+
+OC_EXPORT void oc_oracle_batch_debug_set_t(void **envs, int64_t n, const int32_t *t /*[n]*/) {
+  for (int64_t i = 0; i < n; i++) ((Env *)envs[i])->t = t[i];
+}
+
 OC_EXPORT int oc_oracle_successful(const void *h) { return ((const Env *)h)->successful; }
 OC_EXPORT int oc_oracle_error(const void *h) { return ((const Env *)h)->err; }
 

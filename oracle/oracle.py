@@ -78,6 +78,8 @@ def lib():
         L.oc_oracle_batch_reset.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, _I32P]
         L.oc_oracle_pyset_order.argtypes = [_I32P, ctypes.c_int, _I32P]
         L.oc_oracle_debug_set.argtypes = [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P]
+        L.oc_oracle_debug_set_t.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        L.oc_oracle_batch_debug_set_t.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64, _I32P]
         _lib = L
     return _lib
 
@@ -175,6 +177,11 @@ class OracleEnv:
         gc = np.ascontiguousarray(goal_count if goal_count is not None else np.zeros(self.S), dtype=np.int32)
         lib().oc_oracle_debug_set(self._h, _p32(a), _p32(it), _p32(cs), _p32(gc))
 
+    def set_t(self, t):
+        """TEST ONLY: continue the episode at step counter `t` (oc_oracle_debug_set_t); nothing else
+        changes.  The oracle's counter does not saturate."""
+        lib().oc_oracle_debug_set_t(self._h, int(t))
+
     def step(self, actions):
         act = np.ascontiguousarray(actions, dtype=np.int32)
         r = ctypes.c_int32()
@@ -268,6 +275,12 @@ class OracleBatch:
             a = np.ascontiguousarray(placement, dtype=np.int32)
             assert a.shape == (self.M, self.n)
             lib().oc_oracle_batch_set_placement(self._handles, self.n, _p32(a))
+
+    def set_t(self, t):
+        """TEST ONLY: int32 [n] step counters, one per env (``OracleEnv.set_t``)."""
+        a = np.ascontiguousarray(t, dtype=np.int32)
+        assert a.shape == (self.n,)
+        lib().oc_oracle_batch_debug_set_t(self._handles, self.n, _p32(a))
 
     def snapshot_all(self):
         n, A, M, S = self.n, self.A, self.M, self.S
