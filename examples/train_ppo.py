@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""A learner in the partner seat on one MI355X, without a torch launch on the hot path: the seat acts,
+records and steps inside a captured hipGraph (`FusedActorCriticPartner` + a fused `RolloutSink`), GAE
+is one launch, and every minibatch of the PPO update is three (`PPOLearner`, include/oc_policy.h:
+`oc_policy_ppo_update`).  The ego plays at random.
+
+    python examples/train_ppo.py --envs 4096 --rounds 20
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from gym_comm_amd.arglist import load_env_args
+from gym_comm_amd.vec_env import (FusedActorCriticPartner, MLPActorCritic, OvercookedVecEnv, PPOLearner,
+                                  RandomPartner, RolloutSink)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--level", default="open-divider_tomato")
+    p.add_argument("--envs", type=int, default=4096)
+    p.add_argument("--n-steps", type=int, default=128)
+    p.add_argument("--rounds", type=int, default=20)
+    p.add_argument("--epochs", type=int, default=10)
+    p.add_argument("--batch-size", type=int, default=16384)
+    a = p.parse_args()
+    C = 2
+    cfg = load_env_args({"level": a.level, "num_agents": 2, "max_num_timesteps": 100,
+                         "communication_on": True, "num_communication": C, "fow_radius": 2})
+    venv = OvercookedVecEnv(cfg, a.envs, obs_dtype=torch.float32)
+    sink = RolloutSink(a.n_steps, a.envs, venv._b.F, obs_dtype=torch.float32, fused=True)
+    pol = MLPActorCritic(venv._b.S, C, seed=0).cuda()
+    venv.partner = seat = FusedActorCriticPartner(pol, sample=True, seed=1, sink=sink)
+    learner = PPOLearner(seat, lr=3e-4, ent_coef=0.01)
+    venv.reset_tensors()
+    per = 16 if a.n_steps % 16 == 0 else 1
+    loop = venv.closed_loop(RandomPartner(C, seed=2), steps=per)      # ego -> seat (act, record) -> step, per replay
+    for k in range(a.rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.n_steps // per):                             # collect
+            loop.step()
+        seat.finish_rollout()                                         # GAE: one launch
+        learner.train(sink, n_epochs=a.epochs, batch_size=a.batch_size)
+        sink.reset()
+        st = learner.stats()                                          # the round's only synchronisation
+        dt = time.perf_counter() - t0
+        m = venv.metrics()
+        print("round %3d  %.1f ms  loss %.4f  policy %.4f  value %.4f  entropy %.3f  kl %.4f  clipped %.2f  |g| %.3f  "
+              "episodes %d  reward_sum %d" % (k, dt * 1e3, st["loss"], st["policy_loss"], st["value_loss"],
+                                              -st["entropy_loss"], st["approx_kl"], st["clip_fraction"], st["grad_norm"],
+                                              m["episodes"], m["reward_sum"]))
+
+
+if __name__ == "__main__":
+    main()

@@ -54,6 +54,19 @@ class PolicyAcPlayer(ctypes.Structure):
                 ("comm_row", ctypes.c_void_p), ("log_prob", ctypes.c_void_p), ("value", ctypes.c_void_p)]
 
 
+class PpoCfg(ctypes.Structure):
+    """oc_ppo_cfg (include/oc_policy.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "timestep", "actions", "log_probs", "advantages", "returns")] + \
+               [("n", ctypes.c_int64), ("T", ctypes.c_int32), ("F", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("obs_type", ctypes.c_int32)] + \
+               [(name, ctypes.c_void_p) for name in
+                ("w1", "w2", "b2", "w2t", "p_w1", "p_wt", "p_b1", "p_w2", "p_b2", "p_wv", "p_bv", "m", "v", "step",
+                 "grad", "scratch", "stats", "hyper")] + \
+               [(name, ctypes.c_float) for name in ("ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps")] + \
+               [("max_groups", ctypes.c_int32), ("lp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
+
+
 class RolloutBuf(ctypes.Structure):
     """oc_rollout_buf (include/oc_rollout.h)."""
     _fields_ = [(name, ctypes.c_void_p) for name in
@@ -122,6 +135,10 @@ def _libs_table():
             "oc_policy_pack_w2v": (cint, [fp, fp, i32, vp]),
             "oc_policy_pack_b2v": (cint, [fp, fp, fp, fp, i32, fp]),
             "oc_policy_mlp_ac": (cint, [P(PolicyAcPlayer), i32, vp, i32, i32, i32, i64, vp]),
+            # the PPO update of the actor-critic form
+            "oc_policy_ppo_plan": (cint, [i32, i32, i32, i32, _I32P]),
+            "oc_policy_ppo_update": (cint, [P(PpoCfg), vp, i32, vp]),
+            "oc_policy_ppo_grad": (cint, [P(PpoCfg), vp, i32, vp]),
         }),
         "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
             "oc_hostio_abi_version": (cint, None),

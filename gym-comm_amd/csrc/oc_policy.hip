@@ -84,6 +84,11 @@ uint16_t f32_to_f16_bits(float f) {   // round to nearest even, host side
 
 }  // namespace
 
+// the library's last-error text for its other translation unit (oc_policy_ppo.hip); not exported
+namespace ocpol {
+int host_fail(const char *msg) { return fail(msg); }
+}
+
 extern "C" {
 
 int oc_policy_abi_version(void) { return OC_POLICY_ABI_VERSION; }

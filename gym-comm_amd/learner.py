@@ -1,0 +1,198 @@
+"""``PPOLearner``: the PPO update of a ``FusedActorCriticPartner``'s ``MLPActorCritic`` as three
+launches per minibatch (include/oc_policy.h: ``oc_policy_ppo_update``) -- see ``vec_env`` for the overview."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .batched import OBS_TYPE
+from .partners import FusedActorCriticPartner
+
+STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm",
+         "adv_mean", "adv_std", "bad", "loss")
+PARAMS = ("w1", "wt", "b1", "w2", "b2", "wv", "bv")        # the order of the flat gradient [P]
+
+
+class PPOLearner:
+    """What ``train()`` of the reference's PPO does per minibatch (pantheonrl/algos/modular/learn.py:
+    222-334, stable-baselines3's, ``clip_range_vf=None``, no marginal regularisation) for the module
+    of a ``FusedActorCriticPartner``: advantage normalisation, the clipped loss, its gradient, the
+    norm clip, Adam, and the repack of the seat's fragment tensors -- all on the device, in place,
+    without a synchronisation, capturable into a graph.  The learner owns Adam's ``m``, ``v`` and step
+    counter, the scratch, the statistics and the flat gradient ``grad_flat`` (``grads[name]`` are views of it).
+    ``lr`` and ``clip_range`` live in a device tensor (``hyper``): ``set_lr`` / ``set_clip_range`` are
+    device writes, so a schedule needs no new capture."""
+
+    def __init__(self, seat, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 betas=(0.9, 0.999), eps=1e-5, max_groups=0):
+        if not isinstance(seat, FusedActorCriticPartner):
+            raise TypeError("PPOLearner updates a gym_comm_amd.vec_env.FusedActorCriticPartner")
+        pol = seat.policy
+        self.seat, self.policy = seat, pol
+        self._L = seat._L
+        self.F, self.C = seat.F, seat.C
+        self._params = [getattr(pol, k) for k in PARAMS]
+        for k, t in zip(PARAMS, self._params):
+            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("parameter %s: a contiguous float32 CUDA tensor (there is no CPU fallback)" % k)
+            if t.device != seat._w[0].device:
+                raise ValueError("parameter %s lives on %s, the seat's packed weights on %s" % (k, t.device, seat._w[0].device))
+        dev = self.device = self._params[0].device
+        self._dev = dev.index if dev.index is not None else torch.cuda.current_device()
+        plan = (ctypes.c_int32 * 4)()
+        _lib.check(self._L.oc_policy_ppo_plan(self.F, self.C, 2, 0, plan), "oc_policy_ppo_plan", self._L)
+        P = self.P = int(plan[2])
+        if P != sum(t.numel() for t in self._params):
+            raise ValueError("the module has %d parameters, the kernel's layout %d" % (sum(t.numel() for t in self._params), P))
+        z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
+        self.m, self.v, self.grad_flat = z(P), z(P), z(P)
+        self.step = z(1, torch.int32)
+        self.stats_t = z(len(STATS))
+        self.hyper = torch.tensor([lr, clip_range], dtype=torch.float32, device=dev)
+        self.grads, o = {}, 0
+        for k, t in zip(PARAMS, self._params):
+            self.grads[k] = self.grad_flat[o:o + t.numel()].view(t.shape)
+            o += t.numel()
+        self.ent_coef, self.vf_coef, self.max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
+        self.betas, self.eps, self.max_groups = (float(betas[0]), float(betas[1])), float(eps), int(max_groups)
+        self._scratch, self._retired = None, []
+        self._w2t = z(2 * 16 * 64)
+        self._w2t_src = self._w2t_index()
+        self._cfgs = {}
+        self.lp_out = self.v_out = None          # set to float [B] tensors to receive the forward (tests)
+        self.refresh()
+
+    # ---- the learner's own packed image ----
+    def _w2t_index(self):
+        """For element (m, t, l) of ``w2t``: the index into [w2; wv] flattened, or -1."""
+        src = np.full((2, 16, 64), -1, np.int64)
+        for m in range(2):
+            for t in range(16):
+                for lane in range(64):
+                    row, hid = (t & 3) + 8 * (t >> 2) + 4 * (lane >> 5), 32 * m + (lane & 31)
+                    if row < 4:
+                        src[m, t, lane] = row * 64 + hid
+                    elif row == 8:
+                        src[m, t, lane] = (4 + self.C) * 64 + hid
+                    elif ((row - 4) & 7) < 4:
+                        c = ((row - 4) & 3) + 4 * ((row - 4) >> 3)
+                        if c < self.C:
+                            src[m, t, lane] = (4 + c) * 64 + hid
+        return torch.from_numpy(src.reshape(-1)).to(self.device)
+
+    def refresh(self):
+        """After the module's weights were changed from OUTSIDE (a checkpoint loaded, say): repack the
+        seat's fragments (``seat.refresh()``) and the learner's transposed image.  ``update`` keeps both
+        current itself."""
+        self.seat.refresh()
+        with torch.no_grad():
+            scale = float(np.float32(-2) * np.float32(1.4426950408889634))
+            rows = torch.cat([self.policy.w2.reshape(-1), self.policy.wv.reshape(-1)])
+            folded = (rows * scale).to(torch.float16).to(torch.float32)
+            src = self._w2t_src
+            self._w2t.copy_(torch.where(src >= 0, folded[src.clamp(min=0)], torch.zeros((), device=self.device)))
+
+    # ---- hyper-parameters read on the device ----
+    def set_lr(self, lr):
+        self.hyper[0] = float(lr)
+
+    def set_clip_range(self, clip_range):
+        self.hyper[1] = float(clip_range)
+
+    # ---- one minibatch ----
+    def plan(self, B):
+        """(workgroups, tiles per wave, P, scratch floats) of a minibatch of B samples."""
+        plan = (ctypes.c_int32 * 4)()
+        _lib.check(self._L.oc_policy_ppo_plan(self.F, self.C, int(B), self.max_groups, plan), "oc_policy_ppo_plan", self._L)
+        return tuple(int(v) for v in plan)
+
+    def _cfg(self, sink, B):
+        need = max(self.plan(B)[3], 64 * (self.P + 8))    # the default cap's worth at once: no regrowth
+        if self._scratch is None or self._scratch.numel() < need:
+            self._retired.append(self._scratch)           # a captured graph may still write to it
+            self._scratch = torch.zeros(need, dtype=torch.float32, device=self.device)
+            self._cfgs.clear()
+        key = (id(sink), self.max_groups, None if self.lp_out is None else self.lp_out.data_ptr(),
+               None if self.v_out is None else self.v_out.data_ptr())
+        cfg = self._cfgs.get(key)
+        if cfg is None:
+            for name in ("obs", "timestep", "actions", "log_probs", "advantages", "returns"):
+                t = getattr(sink, name, None)
+                if t is None or t.device != self.device or not t.is_contiguous():
+                    raise ValueError("the sink's %s: a contiguous tensor on %s (a fused sink has advantages / returns)"
+                                     % (name, self.device))
+            T, F, n = sink.obs.shape
+            if F != self.F:
+                raise ValueError("the policy was built for %d observation rows, the sink holds %d" % (self.F, F))
+            if sink.obs.dtype not in OBS_TYPE:
+                raise ValueError("the kernel reads int32, int8 or float32 rows (got %s)" % (sink.obs.dtype,))
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            w = self.seat._w
+            cfg = _lib.PpoCfg(
+                sink.obs.data_ptr(), sink.timestep.data_ptr(), sink.actions.data_ptr(), sink.log_probs.data_ptr(),
+                sink.advantages.data_ptr(), sink.returns.data_ptr(), n, T, F, self.C, OBS_TYPE[sink.obs.dtype],
+                w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr(), self._w2t.data_ptr(),
+                *[t.data_ptr() for t in self._params],
+                self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.grad_flat.data_ptr(),
+                self._scratch.data_ptr(), self.stats_t.data_ptr(), self.hyper.data_ptr(),
+                self.ent_coef, self.vf_coef, self.max_grad_norm, self.betas[0], self.betas[1], self.eps,
+                self.max_groups, ptr(self.lp_out), ptr(self.v_out))
+            cfg._keep = (sink.obs, sink.timestep, sink.actions, sink.log_probs, sink.advantages, sink.returns)
+            self._cfgs[key] = cfg
+        return cfg
+
+    def _run(self, name, sink, idx):
+        if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
+            raise ValueError("idx: a contiguous int32 [B] tensor on %s" % (self.device,))
+        B = idx.numel()
+        for t in (self.lp_out, self.v_out):
+            if t is not None and (t.dtype != torch.float32 or t.numel() < B or not t.is_contiguous()):
+                raise ValueError("lp_out / v_out: contiguous float32 tensors of at least B elements")
+        _lib.call(self._L, name, self._dev, ctypes.byref(self._cfg(sink, B)), idx.data_ptr(), B)
+
+    def update(self, sink, idx):
+        """One minibatch: loss, gradient, clip, Adam, repack.  Three launches, no synchronisation."""
+        self._run("oc_policy_ppo_update", sink, idx)
+
+    def grad(self, sink, idx):
+        """The clipped gradient (``grad_flat`` [P]; ``grads[name]`` are views of it, returned) and the
+        statistics only: a caller with its own optimiser, and the tests."""
+        self._run("oc_policy_ppo_grad", sink, idx)
+        return self.grads
+
+    # ---- epochs ----
+    def minibatches(self, sink, batch_size, granule=32, generator=None):
+        """A device permutation of the sink's T * n samples, cut into int32 index tensors of
+        ``batch_size`` (the last one may be shorter; a remainder of one sample is dropped).
+        ``granule=32`` shuffles tiles of 32 neighbouring envs of a slot -- the envs are independent, and a
+        tile's rows load coalesced; ``granule=1`` is stable-baselines3's full shuffle.  The kernel treats
+        both alike: every lane has its own index."""
+        T, _, n = sink.obs.shape
+        g = int(granule)
+        if g < 1 or n % g:
+            raise ValueError("granule %d does not divide the sink's %d envs" % (g, n))
+        perm = torch.randperm(T * n // g, device=self.device, generator=generator)
+        idx = (perm.unsqueeze(1) * g + torch.arange(g, device=self.device)).reshape(-1).to(torch.int32)
+        return [b for b in idx.split(int(batch_size)) if b.numel() >= 2]
+
+    def train(self, sink, n_epochs=10, batch_size=None, granule=32, generator=None):
+        """``n_epochs`` passes over a FULL fused sink whose ``compute_returns_and_advantage`` has run
+        (``finish_rollout``).  ``batch_size=None``: the whole buffer as one minibatch."""
+        if not getattr(sink, "fused", False):
+            raise ValueError("train() needs a RolloutSink(fused=True): it holds advantages and returns")
+        if not getattr(sink, "returns_ready", False):
+            raise ValueError("train() needs the sink's advantages: call finish_rollout() "
+                             "(compute_returns_and_advantage) first")
+        if not sink.full():
+            raise ValueError("train() needs a full sink (%d of %d steps recorded)" % (sink.steps(), sink.n_steps))
+        T, _, n = sink.obs.shape
+        if granule > 1 and n % granule:
+            granule = 1
+        for _ in range(int(n_epochs)):
+            for idx in self.minibatches(sink, batch_size or T * n, granule, generator):
+                self.update(sink, idx)
+
+    def stats(self):
+        """The last minibatch's statistics as a dict: ONE synchronisation, and only when called."""
+        return dict(zip(STATS, self.stats_t.cpu().tolist()))

@@ -39,6 +39,7 @@ class RolloutSink:
         self.last = z((1,), torch.int64)                 # slot of the most recent add()
         self.count = z((1,), torch.int64)                # adds since reset()
         self.advantages = self.returns = self.ticket = None
+        self.returns_ready = False                       # compute_returns_and_advantage ran since reset()
         self.fused = bool(fused)
         if self.fused:
             # one launch per add / add_reward / compute_returns_and_advantage (include/oc_rollout.h)
@@ -124,6 +125,7 @@ class RolloutSink:
         left as they were.  ``fused=True``: ONE launch, no synchronisation.  Otherwise the loop in
         torch: a few launches per step and one read of the counters -- slow, and the same bits."""
         n = self.obs.shape[2]
+        self.returns_ready = True
         if self.fused:
             keep = (self._row(last_values, torch.float32, n), self._row(dones, torch.float32, n))
             self._call("oc_rollout_gae", keep[0].data_ptr(), keep[1].data_ptr(),
@@ -156,6 +158,7 @@ class RolloutSink:
         return self.steps() >= self.n_steps
 
     def reset(self):
+        self.returns_ready = False
         self.pos.zero_()
         self.last.zero_()
         self.count.zero_()

@@ -31,6 +31,10 @@ Partners
                            the reference seats there: ``OnPolicyAgent(RecurrentPPO(...))``;
   ``FusedMLPPartner``      an ``MLPPolicy`` (64 tanh units) as ONE launch of the hand-written MFMA
                            policy kernel (include/oc_policy.h), ego and partner in the same launch;
+  ``FusedActorCriticPartner``  an ``MLPActorCritic`` in the seat of a player that learns: action,
+                           log-probability and value from one launch, recorded into a ``RolloutSink``;
+                           ``PPOLearner`` (learner.py) is its update: loss, backward, clip, Adam and
+                           the repack of the seat's weights in three launches per minibatch;
   any callable ``partner(obs_dict) -> [n, 2]`` still works (slow path).
 
 ``ClosedLoop`` (``venv.closed_loop(ego)``) captures ego policy -> partner policy -> fused step
@@ -58,6 +62,7 @@ from .envs import OvercookedEnvironment, _arg, make_spaces
 from .partners import (FusedActorCriticPartner, FusedMLPPartner, MLPActorCritic, MLPPolicy,  # noqa: F401 (re-exported)
                        RandomPartner, RecurrentPolicyPartner, TorchPolicyPartner)
 from .rollout import RolloutSink  # noqa: F401 (re-exported)
+from .learner import PPOLearner  # noqa: F401 (re-exported)
 
 try:                                                    # pragma: no cover - SB3 absent in CI image
     from stable_baselines3.common.vec_env import VecEnv as _VecEnvBase

@@ -129,6 +129,93 @@ OC_API int oc_policy_pack_b2v(const float *b2, const float *w2, const float *bv,
 OC_API int oc_policy_mlp_ac(const oc_policy_ac_player *players, int32_t num_players, const double *timestep,
                             int32_t F, int32_t C, int32_t obs_type, int64_t n, void *stream);
 
+/* ---- the PPO update of the actor-critic form: loss, backward, clip, Adam, repack -------------
+ *
+ * What it restates: train() of the reference's PPO (pantheonrl/algos/modular/learn.py:222-334, which
+ * is stable-baselines3's), with clip_range_vf = None and use_sde = False as its trainer configures
+ * it.  OUT OF SCOPE: the marginal-regularisation term (learn.py:299-318, several partners' logits
+ * composed), clip_range_vf, target_kl early stopping (approx_kl is reported for a caller to use),
+ * hidden sizes other than 64.
+ *
+ * A minibatch is idx, int32 [B], B >= 2: sample i is slot idx[i] / n, env idx[i] % n of tensors
+ * shaped as an oc_rollout_buf's (include/oc_rollout.h): obs [T][F][n], timestep double [T][n],
+ * actions int32 [T][2][n], log_probs / advantages / returns float [T][n] (the recorded values are
+ * not read: there is no value clipping).  Any order, repeats allowed; an index outside 0 .. T n - 1
+ * is a caller error and is NOT checked on the device.
+ *
+ * With lp_i, v_i and the heads' probabilities p from the same forward as oc_policy_mlp_ac in `given`
+ * mode (the same operations in the same order: lp_out / v_out are its bits):
+ *     A^_i = (A_i - mean(A)) / (std(A) + 1e-8)        mean and UNBIASED std over the B samples
+ *     rho_i = exp(lp_i - old_lp_i)
+ *     policy_loss  = -mean(min(A^ rho, A^ clamp(rho, 1 - c, 1 + c)))
+ *     value_loss   =  mean((ret_i - v_i)^2)
+ *     entropy_loss = -mean(H_move,i + H_comm,i)        H = -sum_c p_c ln p_c
+ *     loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ * The gradient is taken with respect to the fp32 master weights, flat [P] in this order:
+ * w1 [64][F], wt [64], b1 [64], w2 [4 + C][64], b2 [4 + C], wv [64], bv [1].  It is evaluated at the
+ * network the packed fragments represent -- features, 2 log2(e) W1aug and -2 log2(e) W2 in fp16, r
+ * rounded to fp16 on its way into the second product -- and those roundings are not differentiated
+ * (ordinary mixed precision).  Behind the forward everything is float32 (fp32-operand matrix
+ * products), with h = 1 - 2 r and tanh' = 4 r (1 - r) from the UNROUNDED float32 r:
+ *     d loss / d lp   = -A^ rho / B  where the unclipped term is the minimum or rho lies inside
+ *                       [1 - c, 1 + c], 0 otherwise
+ *     per head:  d lp / d logit_c = 1[c = a] - p_c,   d H / d logit_c = -p_c (ln p_c + H)
+ *     d loss / d v    = 2 vf_coef (v - ret) / B
+ *     columns F and F + 1 of the first layer's augmented gradient are wt and b1.
+ * The 1 / B is applied to the summed gradient, in float32, not to the operands.
+ * A recorded action outside its head's range makes lp = -inf: that sample contributes nothing to any
+ * loss term or gradient and is counted in `bad`; B stays the divisor, and the advantage statistics
+ * (which do not look at actions) still include it.
+ * Clip (clip_grad_norm_): norm = sqrt(sum g^2) over all P, in double; g *= min(1, max_grad_norm /
+ * (norm + 1e-6)).  Adam: torch's, amsgrad = False, no weight decay, in float32; m, v [P] and the int32
+ * step counter live on the device, the bias corrections come from that counter.  Afterwards the
+ * packed w1 / w2 / b2 are rewritten IN PLACE (captured graphs keep the addresses), bit for bit what
+ * oc_policy_pack_w1 / _w2v / _b2v produce on the host from the same fp32 weights, and so is `w2t`,
+ * the learner's own image: float [2][16][64], element (m, t, l) = the fp16 value of -2 log2(e) W2row
+ * [(t & 3) + 8 (t >> 2) + 4 (l >> 5)][32 m + (l & 31)] (the value head is row 8) -- W2 transposed and
+ * k-permuted to the order in which d logits sit in the accumulators.
+ *
+ * stats, float [10], written on the device and never read by the library except [6], [7] within
+ * one call: policy_loss, value_loss, entropy_loss, approx_kl = mean(old_lp - lp), clip_fraction
+ * (|rho - 1| > c), grad_norm (before clipping), adv_mean, adv_std, bad, loss.
+ *
+ * Three launches per minibatch, none allocates or synchronises, all capturable: the advantage
+ * statistics (double, an order fixed by B alone); the loss-and-gradient kernel, whose workgroups
+ * write partials [G][P + 8] to `scratch` (no floating-point atomics: the same call gives the same
+ * bits); one workgroup that sums the partials over g ascending, clips, and (oc_policy_ppo_update) applies
+ * Adam and repacks.  hyper = (lr, clip_range) is read on the device: a schedule needs no new capture. */
+typedef struct {
+  const void *obs;            /* the rollout tensors (above) */
+  const double *timestep;
+  const int32_t *actions;
+  const float *log_probs, *advantages, *returns;
+  int64_t n;
+  int32_t T, F, C, obs_type;  /* obs_type: 0 int32, 1 int8, 2 float32 */
+  uint16_t *w1, *w2;          /* the seat's packed weights (with the value row): read by the forward, */
+  float *b2;                  /*   rewritten by oc_policy_ppo_update */
+  float *w2t;                 /* float [2][16][64], the learner's (above) */
+  float *p_w1, *p_wt, *p_b1, *p_w2, *p_b2, *p_wv, *p_bv;   /* fp32 master weights (oc_policy_ppo_update only) */
+  float *m, *v;               /* Adam state, float [P] each (oc_policy_ppo_update only) */
+  int32_t *step;              /* int32 [1], Adam's step counter (oc_policy_ppo_update only) */
+  float *grad;                /* out: the clipped gradient, float [P] */
+  float *scratch;             /* float [plan[3]] */
+  float *stats;               /* float [10] */
+  const float *hyper;         /* float [2] on the device: lr, clip_range */
+  float ent_coef, vf_coef, max_grad_norm, beta1, beta2, eps;
+  int32_t max_groups;         /* 0 = the library's choice; otherwise a cap on the workgroups */
+  float *lp_out, *v_out;      /* optional out, float [B]: the forward's log_prob and value */
+} oc_ppo_cfg;
+
+/* No device work: plan = (workgroups G of the gradient kernel, tiles of 32 samples per wave, P,
+ * floats of scratch).  Wave w of the 4 G takes tiles w, w + 4 G, ...: no workgroup is empty. */
+OC_API int oc_policy_ppo_plan(int32_t F, int32_t C, int32_t B, int32_t max_groups, int32_t *plan);
+
+/* One minibatch update (3 launches), or the first of it (oc_policy_ppo_grad: the same launches without Adam
+ * and the repack; leaves the clipped gradient and the statistics).  Checked before any device work:
+ * F >= 1, F + 2 <= 48, 1 <= C <= 16, B >= 2, obs_type, T n < 2^31, non-NULL pointers. */
+OC_API int oc_policy_ppo_update(const oc_ppo_cfg *cfg, const int32_t *idx, int32_t B, void *stream);
+OC_API int oc_policy_ppo_grad(const oc_ppo_cfg *cfg, const int32_t *idx, int32_t B, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
