@@ -56,6 +56,34 @@ def nominal_placement(levels, group_map, n):
     return np.ascontiguousarray(cols[env_map].T)
 
 
+class PreparedStep:
+    """A fused step with every argument but the ego's pairs fixed (``BatchedOvercooked.prepare_multi_step``).
+    Calling it -- or its ``launch`` attribute, which saves a frame -- is ``launch(ego_pairs_ptr_or_None,
+    pairs_int64)``.  ``close()`` destroys the native ``oc_call`` behind it, once (a map set's form has
+    none: a no-op there); the batch lists the open ones in ``live`` and closes what is left when it goes.
+    The handle holds the env's tensors by ADDRESS: they must not be rebound while a prepared step is alive."""
+    closed = False
+
+    def __init__(self, launch, lib=None, handle=None, live=None):
+        self.launch, self._lib, self._handle, self._live = launch, lib, handle, live
+        if handle is not None and live is not None:
+            live.append(self)
+
+    def __call__(self, ego_pairs_ptr=None, pairs_int64=False):
+        self.launch(ego_pairs_ptr, pairs_int64)
+
+    @staticmethod
+    def _refuse(ego_pairs_ptr=None, pairs_int64=False):
+        raise RuntimeError("this prepared step was closed")
+
+    def close(self):
+        handle, self._handle, self.launch, self.closed = self._handle, None, self._refuse, True
+        if handle is not None:
+            if self._live is not None:
+                self._live.remove(self)
+            self._lib.oc_call_destroy(handle)
+
+
 class BatchedOvercooked:
     def __init__(self, level, num_agents=2, num_envs=4096, max_num_timesteps=100,
                  ego_config=None, partner_config=None, num_communication=2,
@@ -163,6 +191,7 @@ class BatchedOvercooked:
                                       (2 if self.partner_config["CAN_MOVE"] else 0))
         self._layout = obs_layout(self.S, self.C)
         self._ms_args = None
+        self._prepared = []         # the open PreparedStep objects that hold a native handle
         self._policy_arr = None
         self._arena_pinned = None
         self._fetch_plan = None
@@ -181,9 +210,8 @@ class BatchedOvercooked:
         self.reset()
 
     def __del__(self):
-        for c in getattr(self, "_calls", []):
-            self._L.oc_call_destroy(c)
-        self._calls = []
+        for step in list(getattr(self, "_prepared", [])):
+            step.close()
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             (self._L.oc_mapset_destroy if self.levels else self._L.oc_level_destroy)(h)
@@ -464,14 +492,15 @@ class BatchedOvercooked:
     def prepare_multi_step(self, actions_ptr, alt_rng_ptr=None, alt_played_ptr=None, alt_pairs_ptr=None,
                            auto_reset=True):
         """A PREPARED fused step (include/oc_hip.h: oc_multi_step_prepare): every argument but the ego's
-        pair tensor fixed once; returns ``launch(ego_pairs_ptr_or_None, pairs_int64)`` whose per-call
-        cost is a 4-argument foreign call (the 17-argument one costs a Python caller ~2 us more)."""
+        pair tensor fixed once; returns a ``PreparedStep``: ``launch(ego_pairs_ptr_or_None, pairs_int64)``, whose
+        per-call cost is a 4-argument foreign call (the 17-argument one costs a Python caller ~2 us more), and
+        ``close()``.  The env's tensors must not be rebound while a prepared step is alive."""
         dp = lambda t: 0 if t is None else t.data_ptr()
         if self.levels:     # (no prepared form for map sets: the same launch through multi_step_raw)
             def launch_set(ego_pairs_ptr=None, pairs_int64=False):
                 self.multi_step_raw(actions_ptr or 0, ego_pairs_ptr, alt_pairs_ptr, alt_rng_ptr, alt_played_ptr,
                                     int(auto_reset), pairs_int64)
-            return launch_set
+            return PreparedStep(launch_set)
         opts = _lib.StepOpts(dp(self.ep_return) or None, dp(self.ep_length) or None, None, alt_pairs_ptr,
                              alt_rng_ptr, alt_played_ptr, 0, self.waves_per_64)
         h = ctypes.c_void_p()
@@ -479,8 +508,6 @@ class BatchedOvercooked:
                    ctypes.byref(self._wrap_cfg), dp(self.obs), dp(self.timestep), dp(self.shaped_reward),
                    dp(self.done), dp(self.reward), int(auto_reset), dp(self.metrics), dp(self.placement),
                    dp(self.rng), ctypes.byref(opts), self.n, ctypes.byref(h), stream=False)
-        self._calls = getattr(self, "_calls", [])
-        self._calls.append(h)
         L, dev, call = self._L, self._dev_index, h
         raw_stream = torch._C._cuda_getCurrentRawStream
 
@@ -492,7 +519,7 @@ class BatchedOvercooked:
                     rc = L.oc_call_launch(call, ego_pairs_ptr, 1 if pairs_int64 else 0, raw_stream(dev))
             if rc:
                 _lib.check(rc, "oc_call_launch", L)
-        return launch
+        return PreparedStep(launch, L, h, self._prepared)
 
     def observe_image(self, radius: Optional[int] = None, packed: bool = False):
         """Image-style fog-of-war observation of both viewers

@@ -36,8 +36,8 @@ class PPOLearner:
         for k, t in zip(PARAMS, self._params):
             if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("parameter %s: a contiguous float32 CUDA tensor (there is no CPU fallback)" % k)
-            if t.device != seat._w[0].device:
-                raise ValueError("parameter %s lives on %s, the seat's packed weights on %s" % (k, t.device, seat._w[0].device))
+            if t.device != seat.weight_device:
+                raise ValueError("parameter %s lives on %s, the seat's packed weights on %s" % (k, t.device, seat.weight_device))
         dev = self.device = self._params[0].device
         self._dev = dev.index if dev.index is not None else torch.cuda.current_device()
         plan = (ctypes.c_int32 * 4)()
@@ -128,11 +128,10 @@ class PPOLearner:
             if sink.obs.dtype not in OBS_TYPE:
                 raise ValueError("the kernel reads int32, int8 or float32 rows (got %s)" % (sink.obs.dtype,))
             ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            w = self.seat._w
             cfg = _lib.PpoCfg(
                 sink.obs.data_ptr(), sink.timestep.data_ptr(), sink.actions.data_ptr(), sink.log_probs.data_ptr(),
                 sink.advantages.data_ptr(), sink.returns.data_ptr(), n, T, F, self.C, OBS_TYPE[sink.obs.dtype],
-                w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr(), self._w2t.data_ptr(),
+                *self.seat.weight_ptrs(), self._w2t.data_ptr(),
                 *[t.data_ptr() for t in self._params],
                 self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.grad_flat.data_ptr(),
                 self._scratch.data_ptr(), self.stats_t.data_ptr(), self.hyper.data_ptr(),

@@ -156,7 +156,32 @@ class TorchPolicyPartner(_Seat):
             self.on_update(rewards, dones)
 
 
-class RecurrentPolicyPartner(_Seat):
+class _RecordingSeat(_Seat):
+    """What the two seats that record a rollout share: ``episode_start`` / ``value`` tensors, an optional
+    ``sink`` (a ``RolloutSink``) and an optional host-side ``on_update`` hook."""
+    sink = on_update = None
+
+    def update(self, rewards, dones):
+        """pantheonrl's ``Agent.update(reward, done)`` for the batch: ``dones`` become the next
+        step's ``episode_start`` (agents.py:207-208), the reward joins the recorded transition."""
+        self.episode_start.copy_(dones)
+        if self.sink is not None:
+            self.sink.add_reward(rewards, dones)
+        if self.on_update is not None:
+            self.on_update(rewards, dones)
+
+    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
+        """What ``OnPolicyAgent.get_action`` does on a full buffer before ``train()`` (agents.py:127-131):
+        ``buf.compute_returns_and_advantage(last_values=self.values, dones=self._last_episode_starts[0])``
+        with the values of the last ``act_into`` and the last ``done`` row.  Returns the sink's
+        (advantages, returns); the sink is NOT reset -- the caller does that after its update
+        (agents.py:158)."""
+        if self.sink is None:
+            raise ValueError("finish_rollout needs a sink")
+        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
+
+
+class RecurrentPolicyPartner(_RecordingSeat):
     """A STATEFUL torch policy in the partner (or ego) seat: the batched form of what the
     reference seats there -- ``OnPolicyAgent(RecurrentPPO('MultiInputPolicy', ...))``
     (trainer.py:92-112; pantheonrl/common/agents.py:112-214; sb3_contrib's recurrent policies
@@ -231,25 +256,6 @@ class RecurrentPolicyPartner(_Seat):
             rows, ts = rows_and_timestep(obs)
             self.sink.add(rows, ts, move_row, comm_row, lp, value, es)
 
-    def update(self, rewards, dones):
-        """pantheonrl's ``Agent.update(reward, done)`` for the batch: ``dones`` become the next
-        step's ``episode_start`` (agents.py:207-208), the reward joins the recorded transition."""
-        self.episode_start.copy_(dones)
-        if self.sink is not None:
-            self.sink.add_reward(rewards, dones)
-        if self.on_update is not None:
-            self.on_update(rewards, dones)
-
-    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
-        """What ``OnPolicyAgent.get_action`` does on a full buffer before ``train()`` (agents.py:127-131):
-        ``buf.compute_returns_and_advantage(last_values=self.values, dones=self._last_episode_starts[0])``
-        with the values of the last ``act_into`` and the last ``done`` row.  Returns the sink's
-        (advantages, returns); the sink is NOT reset -- the caller does that after its update
-        (agents.py:158)."""
-        if self.sink is None:
-            raise ValueError("finish_rollout needs a sink")
-        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
-
     def get_state(self, n=None):
         return (tuple(s.clone() for s in self.state), self.episode_start.clone(), self.log_prob.clone(),
                 self.value.clone(), None if self.sink is None else self.sink.get_state())
@@ -264,28 +270,49 @@ class RecurrentPolicyPartner(_Seat):
             self.sink.set_state(st[4])
 
 
-class FusedMLPPartner:
-    """An ``MLPPolicy`` in the partner (or ego) seat as ONE launch of the hand-written policy
-    kernel (include/oc_policy.h, csrc/oc_policy.hip): both products on the matrix cores
-    (v_mfma_f32_32x32x16_f16, one wave = 32 envs, the hidden layer never leaves the accumulator
-    registers), tanh, a categorical sample from two PCG32 streams per env, and the result written as
-    the int32 [n][2] (move, comm) pairs the step kernel consumes as they lie.  What
-    ``TorchPolicyPartner(MLPPolicy(...))`` does in ~12 torch launches.  Two of them (ego + partner)
-    share one launch (``FusedMLPPartner.launch``).  Weights are packed once (``refresh()`` after an
-    optimiser step); fp16 operands, fp32 accumulation: logits within 2e-2 of the fp32 module's."""
-    graph_safe = True
-    _seats = 0          # partners built so far: the default stream seed differs from seat to seat
+def pack_fragments(L, policy, value_head=False):
+    """The module's current weights in MFMA fragment order (include/oc_policy.h: the packers of ``L``,
+    the policy library): numpy ``(o1, o2, ob)`` = first layer (timestep column and bias folded in),
+    second layer, second bias.  ``value_head``: an ``MLPActorCritic``'s value row rides in ``o2`` / ``ob``
+    (``oc_policy_pack_w2v`` / ``_b2v``).  Host code only: no device call."""
+    f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+    fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    F, C = int(policy.w1.shape[1]), int(policy.C)
+    w1, wt, b1, w2, b2 = (f32(t) for t in (policy.w1, policy.wt, policy.b1, policy.w2, policy.b2))
+    o1 = np.zeros((2, L.oc_policy_ksteps(F), 64, 8), np.uint16)
+    o2 = np.zeros((4, 64, 8), np.uint16)
+    ob = np.zeros((64, 16), np.float32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    done = [(L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), F, vp(o1)), "oc_policy_pack_w1")]
+    if value_head:
+        wv, bv = f32(policy.wv).reshape(-1), f32(policy.bv).reshape(-1)
+        done += [(L.oc_policy_pack_w2v(fp(w2), fp(wv), C, vp(o2)), "oc_policy_pack_w2v"),
+                 (L.oc_policy_pack_b2v(fp(b2.reshape(-1)), fp(w2), fp(bv), fp(wv), C, fp(ob)), "oc_policy_pack_b2v")]
+    else:
+        done += [(L.oc_policy_pack_w2(fp(w2), C, vp(o2)), "oc_policy_pack_w2"),
+                 (L.oc_policy_pack_b2(fp(b2.reshape(-1)), fp(w2), C, fp(ob)), "oc_policy_pack_b2")]
+    for rc, what in done:
+        _lib.check(rc, what, L)
+    return o1, o2, ob
 
-    def __init__(self, policy, sample=True, seed=None, device="cuda", keep_logits=False):
-        # seed=None: a different default per partner built (two seats left at their defaults -- an
+
+class _FusedSeat:
+    """What the two seats of the hand-written policy kernel share: the checks of the module, the
+    default stream seed, the packed weights ``_w`` (three device tensors whose addresses never change:
+    ``weight_ptrs()``) and ``refresh()``."""
+    graph_safe = True
+    _module = _module_error = None      # the module class a seat runs, and what it says to any other
+    _value_head = False
+
+    def __init__(self, policy, sample, seed, device, keep_logits):
+        # seed=None: a different default per seat built (two seats left at their defaults -- an
         # ego and a partner -- must not share per-env random streams: their samples would use the
         # same uniform draw every step, ADVICE r2); pass a seed for a reproducible stream
         if seed is None:
             seed = 0x5EED + 1000003 * FusedMLPPartner._seats
         FusedMLPPartner._seats += 1
-        if not isinstance(policy, MLPPolicy):
-            raise TypeError("FusedMLPPartner runs gym_comm_amd.vec_env.MLPPolicy; wrap any other module "
-                            "in TorchPolicyPartner")
+        if not isinstance(policy, self._module):
+            raise TypeError(self._module_error)
         if policy.w1.shape[0] != 64:
             raise ValueError("the fused kernel has 64 hidden units (got %d)" % policy.w1.shape[0])
         if not 1 <= policy.C <= 16:
@@ -297,31 +324,49 @@ class FusedMLPPartner:
         self.F = int(policy.w1.shape[1])
         self.C = int(policy.C)
         self._w = None
-        self._rng = self.pairs = self.logits = None
         self.refresh()
 
     def refresh(self):
         """(Re)pack the module's current weights into MFMA fragment order and upload them."""
-        L, pol = self._L, self.policy
-        f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
-        fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        ks = L.oc_policy_ksteps(self.F)
-        w1, wt, b1, w2, b2 = (f32(t) for t in (pol.w1, pol.wt, pol.b1, pol.w2, pol.b2))
-        o1 = np.zeros((2, ks, 64, 8), np.uint16)
-        o2 = np.zeros((4, 64, 8), np.uint16)
-        ob = np.zeros((64, 16), np.float32)
-        for rc, what in ((L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), self.F,
-                                              o1.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w1"),
-                         (L.oc_policy_pack_w2(fp(w2), self.C, o2.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w2"),
-                         (L.oc_policy_pack_b2(fp(b2.reshape(-1)), fp(w2), self.C, fp(ob)), "oc_policy_pack_b2")):
-            _lib.check(rc, what, L)
-        dev = self.device
-        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(dev) for a in (o1, o2, ob))
+        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
+                    for a in pack_fragments(self._L, self.policy, self._value_head))
         if self._w is None:
             self._w = new
         else:                       # in place: a captured graph keeps the addresses
             for old, cur in zip(self._w, new):
                 old.copy_(cur)
+
+    def weight_ptrs(self):
+        """Device addresses of the three fragment tensors (w1, w2, b2)."""
+        w = self._w
+        return w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr()
+
+    @property
+    def weight_device(self):
+        """Where the fragment tensors live (``device`` with its index resolved)."""
+        return self._w[0].device
+
+    def _check_rows(self, rows):
+        if rows.shape[0] != self.F:
+            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
+
+
+class FusedMLPPartner(_FusedSeat):
+    """An ``MLPPolicy`` in the partner (or ego) seat as ONE launch of the hand-written policy
+    kernel (include/oc_policy.h, csrc/oc_policy.hip): both products on the matrix cores
+    (v_mfma_f32_32x32x16_f16, one wave = 32 envs, the hidden layer never leaves the accumulator
+    registers), tanh, a categorical sample from two PCG32 streams per env, and the result written as
+    the int32 [n][2] (move, comm) pairs the step kernel consumes as they lie.  What
+    ``TorchPolicyPartner(MLPPolicy(...))`` does in ~12 torch launches.  Two of them (ego + partner)
+    share one launch (``FusedMLPPartner.launch``).  Weights are packed once (``refresh()`` after an
+    optimiser step); fp16 operands, fp32 accumulation: logits within 2e-2 of the fp32 module's."""
+    _seats = 0          # fused seats built so far: the default stream seed differs from seat to seat
+    _module = MLPPolicy
+    _module_error = "FusedMLPPartner runs gym_comm_amd.vec_env.MLPPolicy; wrap any other module in TorchPolicyPartner"
+
+    def __init__(self, policy, sample=True, seed=None, device="cuda", keep_logits=False):
+        self._rng = self.pairs = self.logits = None
+        super().__init__(policy, sample, seed, device, keep_logits)
 
     def _buffers(self, n):
         if self.pairs is None or self.pairs.shape[0] != n:
@@ -331,12 +376,9 @@ class FusedMLPPartner:
                            if self.keep_logits else None)
 
     def _player(self, rows):
-        n = rows.shape[1]
-        if rows.shape[0] != self.F:
-            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
-        self._buffers(n)
-        return _lib.PolicyPlayer(rows.data_ptr(), self._w[0].data_ptr(), self._w[1].data_ptr(),
-                                 self._w[2].data_ptr(), self._rng.data_ptr() if self.sample else None,
+        self._check_rows(rows)
+        self._buffers(rows.shape[1])
+        return _lib.PolicyPlayer(rows.data_ptr(), *self.weight_ptrs(), self._rng.data_ptr() if self.sample else None,
                                  self.pairs.data_ptr(), self.logits.data_ptr() if self.logits is not None else None)
 
     @staticmethod
@@ -368,8 +410,7 @@ class FusedMLPPartner:
         """(w1, w2, b2, rng) device addresses for oc_step_opts.policy (the step kernel evaluates
         this policy itself; its result lands in ``self.pairs``)."""
         self._buffers(n)
-        return (self._w[0].data_ptr(), self._w[1].data_ptr(), self._w[2].data_ptr(),
-                self._rng.data_ptr() if self.sample else None)
+        return (*self.weight_ptrs(), self._rng.data_ptr() if self.sample else None)
 
     def pairs_for(self, obs):
         """obs: an ``ObsView`` of the env (``rows`` [F][n], ``timestep``).  Returns int32 [n][2]."""
@@ -395,7 +436,7 @@ class FusedMLPPartner:
         self.pairs.copy_(st[1])
 
 
-class FusedActorCriticPartner(_Seat):
+class FusedActorCriticPartner(_FusedSeat, _RecordingSeat):
     """An ``MLPActorCritic`` in the seat of a player that LEARNS, as ONE launch of the policy kernel's
     actor-critic form (include/oc_policy.h: ``oc_policy_mlp_ac``): what ``OnPolicyAgent.get_action``
     takes from its forward (pantheonrl/common/agents.py:112-194) -- the sampled action, written into
@@ -410,53 +451,14 @@ class FusedActorCriticPartner(_Seat):
     class (pairs consumed as they lie, the step kernel evaluating the policy itself) produce
     neither value nor log-probability.  ``score(obs, pairs)`` evaluates GIVEN actions: what a
     learner's update needs."""
-    graph_safe = True
+    _module = MLPActorCritic
+    _module_error = "FusedActorCriticPartner runs gym_comm_amd.vec_env.MLPActorCritic"
+    _value_head = True          # refresh() packs the value row too
 
     def __init__(self, policy, sample=True, seed=None, device="cuda", sink=None, keep_logits=False):
-        if seed is None:        # as FusedMLPPartner: seats left at their defaults never share streams
-            seed = 0x5EED + 1000003 * FusedMLPPartner._seats
-        FusedMLPPartner._seats += 1
-        if not isinstance(policy, MLPActorCritic):
-            raise TypeError("FusedActorCriticPartner runs gym_comm_amd.vec_env.MLPActorCritic")
-        if policy.w1.shape[0] != 64:
-            raise ValueError("the fused kernel has 64 hidden units (got %d)" % policy.w1.shape[0])
-        if not 1 <= policy.C <= 16:
-            raise ValueError("the fused kernel samples at most 16 comm channels (got %d)" % policy.C)
-        self.policy, self.sample, self.seed = policy, bool(sample), int(seed)
-        self.device = torch.device(device)
         self.sink = sink
-        self.keep_logits = bool(keep_logits)
-        self._L = _lib.load(lib="policy")
-        self.F = int(policy.w1.shape[1])
-        self.C = int(policy.C)
-        self._w = None
         self._rng = self.episode_start = self.log_prob = self.value = self.logits = None
-        self.refresh()
-
-    def refresh(self):
-        """(Re)pack the module's current weights, value row included, and upload them."""
-        L, pol = self._L, self.policy
-        f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
-        fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        ks = L.oc_policy_ksteps(self.F)
-        w1, wt, b1, w2, b2, wv, bv = (f32(t) for t in (pol.w1, pol.wt, pol.b1, pol.w2, pol.b2, pol.wv, pol.bv))
-        o1 = np.zeros((2, ks, 64, 8), np.uint16)
-        o2 = np.zeros((4, 64, 8), np.uint16)
-        ob = np.zeros((64, 16), np.float32)
-        for rc, what in ((L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), self.F,
-                                              o1.ctypes.data_as(ctypes.c_void_p)), "oc_policy_pack_w1"),
-                         (L.oc_policy_pack_w2v(fp(w2), fp(wv.reshape(-1)), self.C, o2.ctypes.data_as(ctypes.c_void_p)),
-                          "oc_policy_pack_w2v"),
-                         (L.oc_policy_pack_b2v(fp(b2.reshape(-1)), fp(w2), fp(bv.reshape(-1)), fp(wv.reshape(-1)),
-                                               self.C, fp(ob)), "oc_policy_pack_b2v")):
-            _lib.check(rc, what, L)
-        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
-                    for a in (o1, o2, ob))
-        if self._w is None:
-            self._w = new
-        else:                       # in place: a captured graph keeps the addresses
-            for old, cur in zip(self._w, new):
-                old.copy_(cur)
+        super().__init__(policy, sample, seed, device, keep_logits)
 
     def _buffers(self, n):
         if self.log_prob is None or self.log_prob.numel() != n:
@@ -469,15 +471,13 @@ class FusedActorCriticPartner(_Seat):
 
     def _launch(self, rows, timestep, given, move_row, comm_row, log_prob, value):
         n = rows.shape[1]
-        if rows.shape[0] != self.F:
-            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
+        self._check_rows(rows)
         if not rows.is_contiguous():
             raise ValueError("the kernel reads the observation rows as they lie: [F][n], contiguous")
         ptr = lambda t: None if t is None else t.data_ptr()
         use_rng = self.sample and given is None
         pl = _lib.PolicyAcPlayer(
-            _lib.PolicyPlayer(rows.data_ptr(), self._w[0].data_ptr(), self._w[1].data_ptr(), self._w[2].data_ptr(),
-                              self._rng.data_ptr() if use_rng else None, None,
+            _lib.PolicyPlayer(rows.data_ptr(), *self.weight_ptrs(), self._rng.data_ptr() if use_rng else None, None,
                               ptr(self.logits) if given is None else None),
             ptr(given), ptr(move_row), ptr(comm_row), ptr(log_prob), ptr(value))
         _lib.call(self._L, "oc_policy_mlp_ac", rows.device.index, ctypes.byref(pl), 1, timestep.data_ptr(),
@@ -521,18 +521,9 @@ class FusedActorCriticPartner(_Seat):
             self.episode_start.fill_(1.0)
 
     def update(self, rewards, dones):
-        """pantheonrl's ``Agent.update(reward, done)`` for the batch (``RecurrentPolicyPartner.update``)."""
+        """pantheonrl's ``Agent.update(reward, done)`` for the batch, on buffers that exist by now."""
         self._buffers(dones.numel())
-        self.episode_start.copy_(dones)
-        if self.sink is not None:
-            self.sink.add_reward(rewards, dones)
-
-    def finish_rollout(self, gamma=0.99, gae_lambda=0.95):
-        """``RecurrentPolicyPartner.finish_rollout``: the sink's (advantages, returns) with the values
-        of the last ``act_into`` and the last ``done`` row; the sink is not reset."""
-        if self.sink is None:
-            raise ValueError("finish_rollout needs a sink")
-        return self.sink.compute_returns_and_advantage(self.value, self.episode_start, gamma, gae_lambda)
+        super().update(rewards, dones)
 
     def get_state(self, n):
         """The seat's mutable state: its random streams, ``episode_start``, the last ``log_prob`` /

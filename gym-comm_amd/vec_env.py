@@ -36,28 +36,30 @@ Partners
                            ``PPOLearner`` (learner.py) is its update: loss, backward, clip, Adam and
                            the repack of the seat's weights in three launches per minibatch;
   any callable ``partner(obs_dict) -> [n, 2]`` still works (slow path).
+How a seated player yields its actions -- pairs consumed as they lie, ``act_into`` on the action
+rows, a callable -- is decided in one place, ``seat_actions``, for the partner's seat and the ego's.
 
 ``ClosedLoop`` (``venv.closed_loop(ego)``) captures ego policy -> partner policy -> fused step
 (+ in-kernel episode statistics) in one hipGraph, so a rollout costs one graph replay per step
-(or per k steps) instead of a dozen host-side launches.
+(or per k steps) instead of a dozen host-side launches.  A loop keeps the partner it was built
+with; assigning ``venv.partner`` retires the env's loops and closes its prepared step.
 
 Subclasses ``stable_baselines3.common.vec_env.VecEnv`` when SB3 is importable; otherwise a
 structural stand-in with the same methods.  ``step_tensors`` is the zero-copy variant for
-policies that live on the GPU; the numpy API packs a step's arrays with one launch of
-``oc_pack_host`` (include/oc_hostio.h) and one PCIe copy -- or, with ``host_io="mapped"``, has
-the kernels read the actions from host-mapped memory and write the packed step into it, and
-finishes the step by polling an event (no copy, no blocking wait).
+policies that live on the GPU.  The numpy API is ``hostio.py``'s: a transport, built on the first
+numpy call, packs a step's arrays with one launch of ``oc_pack_host`` (include/oc_hostio.h) and one
+PCIe copy (``HostCopy``) -- or, with ``host_io="mapped"`` (``HostMapped``), has the kernels read the
+actions from host-mapped memory and write the packed step into it, and finishes the step by polling
+an event (no copy, no blocking wait).  This class validates, assembles ``infos`` and calls it.
 """
-import ctypes
 import os
-import time
 import weakref
 
 import numpy as np
 import torch
 
-from . import _lib
-from .batched import BatchedOvercooked, OBS_TYPE
+from .batched import BatchedOvercooked
+from .hostio import MappedBuffer, SPACE_DTYPE, TRANSPORTS  # noqa: F401 (re-exported)
 from .envs import OvercookedEnvironment, _arg, make_spaces
 from .partners import (FusedActorCriticPartner, FusedMLPPartner, MLPActorCritic, MLPPolicy,  # noqa: F401 (re-exported)
                        RandomPartner, RecurrentPolicyPartner, TorchPolicyPartner)
@@ -78,16 +80,6 @@ except Exception:
             return self.step_wait()
 
 
-# dtype each key has after SB3 copies it into a buffer of the declared space
-# (gym_comm/envs/overcooked_env.py:41-85: Box float32 / Box int64 / MultiBinary int8)
-SPACE_DTYPE = {
-    "timestep": np.float32, "object_encodings_x": np.int64, "object_encodings_y": np.int64,
-    "state_encodings": np.int8, "is_hidden": np.int8, "completed_subtasks": np.int8,
-    "agent1_location": np.float32, "agent2_location": np.float32, "agent_is_holding": np.int8,
-    "agent1_comm": np.int8, "agent2_comm": np.int8,
-}
-
-
 class ObsView(dict):
     """One viewer's observation: the 11 keys of get_observation2 as [n, k] tensor views, plus
     the storage they are views of -- ``rows`` ([F][n], the kernel's env-major rows; a policy
@@ -97,65 +89,71 @@ class ObsView(dict):
     timestep = None
 
 
-class MappedBuffer:
-    """``nbytes`` of pinned host memory that kernels read and write in place (include/oc_hostio.h:
-    ``oc_hostio_alloc``): ``dev`` is its address for kernels, ``view()`` a uint8 array over it for
-    the host.  The object is the ``base`` of that array and so of every array cut from it: the
-    memory is freed when the last of them and the last other reference to the object are gone.
-    Nothing here waits for a kernel that may still be writing it (an env dropped between
-    ``step_async`` and ``step_wait``): ``hipHostFree`` synchronises the device before it releases
-    the memory, and that is what this relies on."""
-
-    def __init__(self, L, dev_index, nbytes):
-        host, dev = ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.call(L, "oc_hostio_alloc", dev_index, int(nbytes), ctypes.byref(host), ctypes.byref(dev), stream=False)
-        self._L, self.host, self.dev, self.nbytes = L, host.value, dev.value, int(nbytes)
-
-    @property
-    def __array_interface__(self):
-        return {"shape": (self.nbytes,), "typestr": "|u1", "data": (self.host, False), "version": 3}
-
-    def view(self):
-        return np.asarray(self)
-
-    def __del__(self):
-        host, self.host = getattr(self, "host", None), None
-        if host:
-            try:
-                self._L.oc_hostio_free(host)
-            except Exception:                   # interpreter shutdown
-                pass
+def seat_actions(player, obs, rows):
+    """How a seated player produces its (move, comm): the ONE place that knows.  ``obs``: the viewer's
+    ``ObsView``; ``rows``: int32 [2][n], that seat's move and comm rows of the kernel's action tensor.
+    Returns int32 [n][2] pairs for the step kernel to consume as they lie, or None after writing
+    ``rows``.  A ``FusedMLPPartner`` yields its pairs (one launch); anything with ``act_into(obs,
+    move_row, comm_row)`` writes the rows; a bare callable ``player(obs) -> [n, 2]`` is taken as it
+    lies when int32 and contiguous, and copied into the rows otherwise.  (The in-kernel partner and
+    the joint launch of two fused policies are decided in front of this, where they apply.)"""
+    if isinstance(player, FusedMLPPartner):
+        return player.pairs_for(obs)
+    act_into = getattr(player, "act_into", None)
+    if act_into is not None:
+        act_into(obs, rows[0], rows[1])
+        return None
+    pa = torch.as_tensor(player(obs), device=rows.device)
+    if pa.dtype == torch.int32 and pa.is_contiguous():
+        return pa
+    rows.copy_(pa.T)
+    return None
 
 
 class ClosedLoop:
     """ego policy -> partner policy -> fused step, ``steps`` times, as ONE hipGraph.
 
-    ``ego``: something with ``act_into(obs, move_row, comm_row)`` (``TorchPolicyPartner``,
-    ``RandomPartner``), or None -- then the caller writes the ego's (move, comm) into
-    ``venv.ego_action_rows`` before every ``step()``.  ``enqueue()`` issues the launches of one
-    step eagerly (what gets captured; also usable inside a caller's own capture)."""
+    ``ego``: any player ``seat_actions`` takes (``TorchPolicyPartner``, ``RandomPartner``, a
+    ``FusedMLPPartner``, anything with ``act_into``, a callable), or None -- then the caller writes
+    the ego's (move, comm) into ``venv.ego_action_rows`` before every ``step()``.  ``enqueue()``
+    issues the launches of one step eagerly (what gets captured; also usable inside a caller's own
+    capture).
+
+    The loop keeps the partner it was built -- and captured -- with (``self.partner``).  Replacing
+    ``venv.partner`` RETIRES every live loop of that env: ``step()`` / ``enqueue()`` then raise, and
+    ``reset_tensors()`` no longer looks at it; build a new loop.  Two live one-launch loops that
+    share players on one env are not supported: each would rewind the shared streams at a reset."""
+    retired = False
+    _RETIRED = ("the env's partner was replaced after this loop was built (and captured): build a new loop "
+                "with venv.closed_loop(...)")
 
     def __init__(self, venv, ego=None, graph=True, steps=1, one_launch=None):
         self.venv, self.ego, self.steps = venv, ego, int(steps)
+        self.partner = venv.partner
         self.graph = None
         # ego and partner both FusedMLPPartner: let the step kernel evaluate them (one launch per
         # step instead of two) where the library can -- a specialised one, at most 4 comm channels --
         # and where it pays: in a split launch each of the four waves takes one (viewer, half)
         # pass (7.7 -> 6.7 us per step at 4 096 envs); a lone wave per 64 envs would run all four
         # passes back to back (9.6 -> 13.7 us at 32 768 envs), so larger batches keep two launches
-        pt = venv.partner
-        can = (isinstance(ego, FusedMLPPartner) and isinstance(pt, FusedMLPPartner) and pt.F == ego.F
-               and pt.C == ego.C and ego.C <= 4 and venv._b.kernel_flavour == "spec"
+        pt = self.partner
+        # two fused policies of one shape share ONE launch of the policy kernel (or of the step kernel)
+        self._joint = (isinstance(ego, FusedMLPPartner) and isinstance(pt, FusedMLPPartner) and pt.F == ego.F
+                       and pt.C == ego.C)
+        can = (self._joint and ego.C <= 4 and venv._b.kernel_flavour == "spec"
                and venv._b.standard_wrapper_config and not venv._b.levels)     # (a map set has no fused policies)
         if one_launch and not can:
             raise ValueError("one_launch needs two FusedMLPPartner of one shape, C <= 4, a specialised library, "
                              "the wrapper's standard configuration and a single level (no map set)")
         self.one_launch = (can and venv._b.launch_waves(general=True) == 4) if one_launch is None else bool(one_launch)
+        # MultiAgentEnv._update_players (multiagentenv.py:186-195): every seated agent hears the step's
+        # reward and done -- inside the captured graph when the player's update() is device work
+        self._updates = [pl.update for pl in (ego, pt) if pl is not None and hasattr(pl, "update")]
         self._primed = False
         self.prime()
         venv._loops.add(self)       # reset_tensors() re-primes every live loop (weak references)
         if graph:
-            for pl in (ego, venv.partner):
+            for pl in (ego, pt):
                 if pl is not None and not getattr(pl, "graph_safe", False):
                     raise ValueError("%r is not marked graph_safe (stateless, fixed-shape)" % (pl,))
             self.graph = venv._capture(self.enqueue, players=[ego], repeat=self.steps)
@@ -175,46 +173,42 @@ class ClosedLoop:
             # the pending pairs being replaced consumed one draw of each stream: take it back, so the
             # re-evaluation on the new observations uses the draw the two-launch form would use next
             self.ego.rewind_rng()
-            v.partner.rewind_rng()
+            self.partner.rewind_rng()
         o0, o1 = v._obs_tensors(0), v._obs_tensors(1)
-        FusedMLPPartner.launch([self.ego, v.partner], [o0.rows, o1.rows], o0.timestep)
+        FusedMLPPartner.launch([self.ego, self.partner], [o0.rows, o1.rows], o0.timestep)
         self._primed = True
 
     def enqueue(self):
+        if self.retired:
+            raise RuntimeError(self._RETIRED)
         v = self.venv
-        ego, pt = self.ego, v.partner
-        if isinstance(ego, FusedMLPPartner):
-            if isinstance(pt, FusedMLPPartner) and pt.F == ego.F and pt.C == ego.C:
-                o0, o1 = v._obs_tensors(0), v._obs_tensors(1)
-                if self.one_launch:
-                    # the step kernel evaluates both policies itself, behind the step, on the
-                    # observations it has just written, and leaves the NEXT step's pairs in
-                    # ego.pairs / pt.pairs (oc_step_opts.policy): ONE launch per step.  (The pairs
-                    # of the very first step came from one launch of the policy kernel: __init__.)
-                    n = v.num_envs
-                    v._b.multi_step(v._act, ego_pairs=ego.pairs, alt_pairs=pt.pairs,
-                                    policy=(ego.step_policy(n), pt.step_policy(n)))
-                else:
-                    # both policies in ONE launch, their pairs consumed by the step as they lie
-                    FusedMLPPartner.launch([ego, pt], [o0.rows, o1.rows], o0.timestep)
-                    v._b.multi_step(v._act, ego_pairs=ego.pairs, alt_pairs=pt.pairs)
+        ego, pt = self.ego, self.partner
+        if self._joint:
+            o0, o1 = v._obs_tensors(0), v._obs_tensors(1)
+            if self.one_launch:
+                # the step kernel evaluates both policies itself, behind the step, on the
+                # observations it has just written, and leaves the NEXT step's pairs in
+                # ego.pairs / pt.pairs (oc_step_opts.policy): ONE launch per step.  (The pairs
+                # of the very first step came from one launch of the policy kernel: __init__.)
+                n = v.num_envs
+                v._b.multi_step(v._act, ego_pairs=ego.pairs, alt_pairs=pt.pairs,
+                                policy=(ego.step_policy(n), pt.step_policy(n)))
             else:
-                v._partner_and_step(ego.pairs_for(v._obs_tensors(0)))
-        else:
-            if ego is not None:
-                ego.act_into(v._obs_tensors(0), v._act[0], v._act[1])
-            v._partner_and_step(None)
-        # MultiAgentEnv._update_players (multiagentenv.py:186-195): every seated agent hears the
-        # step's reward and done -- inside the captured graph when the player's update() is device work
-        for pl in (ego, pt):
-            if pl is not None and hasattr(pl, "update"):
-                pl.update(v._b.shaped_reward, v._b.done)
+                # both policies in ONE launch, their pairs consumed by the step as they lie
+                FusedMLPPartner.launch([ego, pt], [o0.rows, o1.rows], o0.timestep)
+                v._b.multi_step(v._act, ego_pairs=ego.pairs, alt_pairs=pt.pairs)
+        else:       # (ego None: the caller wrote the ego's rows)
+            v._partner_and_step(None if ego is None else seat_actions(ego, v._obs_tensors(0), v._seat_rows[0]))
+        for update in self._updates:
+            update(v._b.shaped_reward, v._b.done)
         v._version += 1
 
     def step(self):
         """Returns (ego obs, shaped reward f64 [n], done int32 [n]) -- views of the tensors the
         next step overwrites."""
         v = self.venv
+        if self.retired:
+            raise RuntimeError(self._RETIRED)
         if self.graph is not None:
             self.graph.replay()
             v._version += self.steps
@@ -247,9 +241,8 @@ class OvercookedVecEnv(_VecEnvBase):
         blocking wait.  ``"mapped"``: the step kernel reads the actions from host-mapped memory,
         ``oc_pack_host_tiled`` writes the packed step into one of two alternating host-mapped
         buffers, ``step_async`` starts that work and ``step_wait`` polls for its end."""
-        if host_io not in ("copy", "mapped"):
+        if host_io not in tuple(TRANSPORTS):
             raise ValueError("host_io must be \"copy\" or \"mapped\", not %r" % (host_io,))
-        self._host_io = host_io
         if _arg(arglist, "num_agents") != 2:
             raise ValueError("the gym_comm wrapper drives exactly 2 agents")
         self.arglist = arglist
@@ -278,38 +271,38 @@ class OvercookedVecEnv(_VecEnvBase):
         self._loops = weakref.WeakSet()                  # live ClosedLoop objects (re-primed by reset_tensors)
         self.partner = partner if partner is not None else RandomPartner(self._b.C, seed, self._b.device)
         self._act = torch.zeros((4, num_envs), dtype=torch.int32, device=self._b.device)
-        self._pending = None
+        self._seat_rows = (self._act[0:2], self._act[2:4])     # (move, comm) rows of the ego and of the partner
         # the kernel overwrites the same observation rows every step, so the 11-key views of
         # both viewers are built once (22 slice + transpose objects cost ~60 us per step otherwise)
         self._views = [None, None]
         self._infos = [{} for _ in range(num_envs)]      # reused; only finished envs are touched
         self._dirty = []
-        self._host_plan_cache = None
         self._last_terminal = None
         self._version = 0                                # bumped by every step / reset
         self._env_views = {}                             # env index -> (OvercookedEnvironment view, version)
         self._env_attrs = {}                             # (env index, name) -> value set by set_attr(indices=...)
         self._use_graph = bool(use_graph) and not self.terminal_obs
         self._ego_pairs = None
-        self._act_pinned = None
-        self._host_stats = None
-        # numpy API: False = every step returns fresh arrays (a host copy out of the pinned
-        # buffer); True = the arrays are views of two alternating pinned buffers, valid until
-        # the step after next (what a rollout collector that copies them on arrival needs);
-        # host_io="mapped": the same of two host-mapped buffers (then the same array objects every other step)
-        self._reuse_host = bool(reuse_host_buffers)
-        self._host_flip = 0
-        self._act_mapped = None                          # host_io="mapped": the actions' MappedBuffer
-        self._inflight = None                            # ... and the step started by step_async
+        # the numpy API's transport (hostio.py), built on first use: tensor-only users allocate no pinned
+        # or mapped memory.  reuse_host_buffers: False = every step returns fresh arrays; True = the arrays
+        # are views of two alternating buffers, valid until the step after next
+        self._io, self._io_args = None, (TRANSPORTS[host_io], bool(reuse_host_buffers))
 
     @property
     def partner(self):
         return self._partner
 
     @partner.setter
-    def partner(self, pt):          # a new partner invalidates the prepared launch plan / captured graph
+    def partner(self, pt):
+        """A new partner invalidates what was prepared or captured with the old one: the prepared
+        single-launch step is closed, the captured step dropped, every live ``ClosedLoop`` retired."""
         self._partner = pt
+        if self._fast:
+            self._fast["prepared"].close()
         self._fast = self._graph = None
+        for lp in list(self._loops):
+            lp.retired = True
+        self._loops.clear()
 
     # the running episode statistics live in the batch (kept by the kernel)
     @property
@@ -367,12 +360,11 @@ class OvercookedVecEnv(_VecEnvBase):
         if self._use_graph or self.terminal_obs or not getattr(pt, "in_kernel", False) or hasattr(pt, "update"):
             return False
         rng = pt.rng_state(self.num_envs).data_ptr()
-        return {"act": self._act.data_ptr(), "played": self._act[2:4].data_ptr(),
-                "rng": rng, "obs": self._obs_tensors(0),
-                "pair_shape": torch.Size((self.num_envs, 2)), "dev": self._b._dev_index,
+        prepared = self._b.prepare_multi_step(self._act.data_ptr(), alt_rng_ptr=rng,
+                                              alt_played_ptr=self._act[2:4].data_ptr(), auto_reset=True)
+        return {"obs": self._obs_tensors(0), "pair_shape": torch.Size((self.num_envs, 2)), "dev": self._b._dev_index,
                 # the prepared call (include/oc_hip.h: oc_multi_step_prepare): everything but the ego's pairs fixed
-                "launch": self._b.prepare_multi_step(self._act.data_ptr(), alt_rng_ptr=rng,
-                                                     alt_played_ptr=self._act[2:4].data_ptr(), auto_reset=True)}
+                "prepared": prepared, "launch": prepared.launch}
 
     def _capture(self, fn, players=(), repeat=1):
         """`repeat` calls of fn() as one hipGraph.  One eager warm-up call first (module loads,
@@ -416,18 +408,8 @@ class OvercookedVecEnv(_VecEnvBase):
             b.multi_step(self._act, auto_reset=auto_reset, ego_pairs=ego_pairs,
                          alt_rng=pt.rng_state(self.num_envs), alt_played=self._act[2:4])
             return
-        partner_obs = self._obs_tensors(1)
-        alt_pairs = None
-        if isinstance(pt, FusedMLPPartner):       # one launch; its pairs are consumed as they lie
-            alt_pairs = pt.pairs_for(partner_obs)
-        elif hasattr(pt, "act_into"):     # rows of the action tensor: ego move, ego comm, alt move, alt comm
-            pt.act_into(partner_obs, self._act[2], self._act[3])
-        else:
-            pa = torch.as_tensor(pt(partner_obs), device=b.device)
-            if pa.dtype == torch.int32 and pa.is_contiguous():
-                alt_pairs = pa                               # consumed as it lies
-            else:
-                self._act[2:4].copy_(pa.T)
+        # rows of the action tensor: ego move, ego comm, alt move, alt comm
+        alt_pairs = seat_actions(pt, self._obs_tensors(1), self._seat_rows[1])
         b.multi_step(self._act, auto_reset=auto_reset, ego_pairs=ego_pairs, alt_pairs=alt_pairs)
 
     def _staged_pairs(self):
@@ -436,6 +418,12 @@ class OvercookedVecEnv(_VecEnvBase):
         if self._ego_pairs is None:
             self._ego_pairs = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self._b.device)
         return self._ego_pairs
+
+    def _single_launch(self):
+        """``_fast_plan()``, made once per partner."""
+        if self._fast is None:
+            self._fast = self._fast_plan()
+        return self._fast
 
     def _fast_step(self, f, ego_ptr, pairs_int64):
         """The single-launch step of ``_fast_plan()`` on the ego pairs at device address ``ego_ptr``
@@ -461,10 +449,8 @@ class OvercookedVecEnv(_VecEnvBase):
                 if not (isinstance(ea, torch.Tensor) and (ea.dtype is torch.int32 or ea.dtype is torch.int64)
                         and ea.is_cuda and ea.is_contiguous() and ea.shape == f["pair_shape"]
                         and ea.get_device() == f["dev"]):
-                    if self._ego_pairs is None:
-                        self._ego_pairs = torch.zeros(f["pair_shape"], dtype=torch.int32, device=b.device)
-                    self._ego_pairs.copy_(torch.as_tensor(ego_actions, device=b.device))
-                    ea = self._ego_pairs
+                    ea = self._staged_pairs()
+                    ea.copy_(torch.as_tensor(ego_actions, device=b.device))
                 ego_ptr = ea.data_ptr()
                 i64 = ea.dtype is torch.int64
             return self._fast_step(f, ego_ptr, ego_ptr is not None and i64)
@@ -510,168 +496,22 @@ class OvercookedVecEnv(_VecEnvBase):
     def _to_numpy(obs):
         return {k: v.cpu().numpy().astype(SPACE_DTYPE[k]) for k, v in obs.items()}
 
-    def _host_plan(self):
-        """The pack plan of the numpy boundary (include/oc_hostio.h): which observation row goes
-        to which column of which dtype block (int64 / float32 / int8 as the declared spaces,
-        overcooked_env.py:41-85), the device and pinned host buffers, and the numpy views' offsets."""
-        b, n = self._b, self.num_envs
-        L = _lib.load(lib="hostio")
-        block_of = {np.dtype(np.int64): 0, np.dtype(np.float32): 1, np.dtype(np.int8): 2}
-        width, plan, cols = [0, 0, 0], np.zeros(b.F, np.int32), {}
-        for k, (lo, hi) in b._layout.items():
-            blk = block_of[np.dtype(SPACE_DTYPE[k])]
-            cols[k] = (blk, width[blk], width[blk] + hi - lo)
-            for r in range(lo, hi):
-                plan[r] = (blk << 16) | width[blk]
-                width[blk] += 1
-        stats = b.ep_return is not None
-        total = int(L.oc_pack_host_bytes(width[0], width[1], width[2], 1, int(stats), 1, int(stats), n))
-        off, o = {}, 0
-        for name, nbytes in (("b64", n * width[0] * 8), ("ret", n * 8 if stats else 0), ("b32", n * width[1] * 4),
-                             ("ts", n * 4), ("rew", n * 4), ("done", n * 4), ("len", n * 4 if stats else 0),
-                             ("b8", n * width[2])):
-            off[name] = (o, o + nbytes)
-            o += nbytes
-        assert o == total
-        hp = {"L": L, "plan": torch.from_numpy(plan).to(b.device), "width": width, "cols": cols, "stats": stats,
-              "off": off, "ot": OBS_TYPE[b.obs.dtype]}
-        if self._host_io == "mapped":
-            # two host-mapped buffers the pack kernel writes in turn, and the event that ends a step
-            hp["mapped"] = [MappedBuffer(L, b._dev_index, max(total, 1)) for _ in range(2)]
-            hp["event"] = torch.cuda.Event()
-            hp["views"] = [None, None]
-        else:
-            hp["dev"] = torch.empty(max(total, 1), dtype=torch.uint8, device=b.device)
-            hp["pinned"] = [torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
-                            for _ in range(2 if self._reuse_host else 1)]
-        return hp
-
-    def _host_step(self, rew=None, done=None):
-        """Everything the numpy API returns for one step: ONE launch (``oc_pack_host``,
-        include/oc_hostio.h: the ego viewer's [F][n] rows gathered by target dtype, transposed
-        and converted; float32 timestep and reward, done flags, episode return / length) into one
-        device buffer, ONE device->host copy into pinned memory, and a host copy out of it (the
-        caller may keep the arrays); the per-key arrays are column views of that copy."""
-        b, n = self._b, self.num_envs
-        hp = self._host_plan_cache
-        if hp is None:
-            hp = self._host_plan_cache = self._host_plan()
-        dp = lambda t: None if t is None else t.data_ptr()
-        _lib.call(hp["L"], "oc_pack_host", b._dev_index, b.obs[0].data_ptr(), hp["ot"], b.F, hp["plan"].data_ptr(),
-                  hp["width"][0], hp["width"][1], hp["width"][2], b.timestep.data_ptr(),
-                  b.shaped_reward.data_ptr(), dp(b.ep_return), b.done.data_ptr(), dp(b.ep_length),
-                  hp["dev"].data_ptr(), n)
-        self._host_flip ^= 1
-        pinned = hp["pinned"][self._host_flip if self._reuse_host else 0]
-        pinned.copy_(hp["dev"], non_blocking=True)
-        torch.cuda.current_stream(b.device).synchronize()
-        host = pinned.numpy() if self._reuse_host else pinned.numpy().copy()
-        return self._host_views(hp, host, rew, done)
-
-    def _host_views(self, hp, host, rew, done):
-        """The per-key arrays, rewards and done flags as views of one packed step ``host`` (uint8)."""
-        n = self.num_envs
-        view = lambda name, dt, shape: host[hp["off"][name][0]:hp["off"][name][1]].view(dt).reshape(shape)
-        blocks = (view("b64", np.int64, (n, hp["width"][0])), view("b32", np.float32, (n, hp["width"][1])),
-                  view("b8", np.int8, (n, hp["width"][2])))
-        obs = {k: blocks[blk][:, lo:hi] for k, (blk, lo, hi) in hp["cols"].items()}
-        obs["timestep"] = view("ts", np.float32, (n, 1))
-        self._host_stats = ((view("ret", np.float64, (n,)), view("len", np.int32, (n,))) if hp["stats"] else None)
-        return (obs, view("rew", np.float32, (n,)) if rew is not None else None,
-                view("done", np.int32, (n,)) if done is not None else None)
-
-    def _mapped_pack(self):
-        """host_io="mapped", first half: ``oc_pack_host_tiled`` straight into the next of the two
-        host-mapped buffers, and an event behind it."""
-        b = self._b
-        hp = self._host_plan_cache
-        if hp is None:
-            hp = self._host_plan_cache = self._host_plan()
-        dp = lambda t: None if t is None else t.data_ptr()
-        self._host_flip ^= 1
-        _lib.call(hp["L"], "oc_pack_host_tiled", b._dev_index, b.obs[0].data_ptr(), hp["ot"], b.F,
-                  hp["plan"].data_ptr(), hp["width"][0], hp["width"][1], hp["width"][2], b.timestep.data_ptr(),
-                  b.shaped_reward.data_ptr(), dp(b.ep_return), b.done.data_ptr(), dp(b.ep_length),
-                  hp["mapped"][self._host_flip].dev, self.num_envs)
-        hp["event"].record(torch.cuda.current_stream(b.device))
-
-    def _mapped_wait(self, rew=None, done=None, timeout=30.0):
-        """host_io="mapped", second half: poll the event (a blocked wait on this runtime can return
-        tens of milliseconds late), then the views of the buffer just written."""
-        hp = self._host_plan_cache
-        ev = hp["event"]
-        deadline = time.monotonic() + timeout
-        while not ev.query():
-            if time.monotonic() > deadline:
-                raise RuntimeError("host_io=\"mapped\": the step did not finish within %g s" % timeout)
-        host = hp["mapped"][self._host_flip].view()
-        if not self._reuse_host:
-            return self._host_views(hp, host.copy(), rew, done)
-        # views of the two buffers are the same arrays every other step: cut them once per buffer
-        cut = hp["views"][self._host_flip]
-        if cut is None:
-            cut = hp["views"][self._host_flip] = self._host_views(hp, host, True, True) + (self._host_stats,)
-        obs, rew_np, done_np, self._host_stats = cut
-        return dict(obs), rew_np if rew is not None else None, done_np if done is not None else None
-
-    def _ego_obs_numpy(self):
-        if self._host_io == "mapped":
-            if self._inflight is not None:          # a step nobody waited for: let it end first
-                self._mapped_wait()
-                self._inflight = None
-            self._mapped_pack()
-            return self._mapped_wait()[0]
-        return self._host_step()[0]
+    def _transport(self):
+        """The numpy boundary's transport (hostio.py: ``HostCopy`` or ``HostMapped``), built on first use."""
+        if self._io is None:
+            cls, reuse = self._io_args
+            self._io = cls(weakref.proxy(self), reuse)
+        return self._io
 
     def reset(self):
         self.reset_tensors()
-        return self._ego_obs_numpy()
+        return self._transport().observe()
 
     def step_async(self, actions):
-        if self._host_io == "mapped":
-            return self._mapped_step_async(actions)
-        self._pending = np.asarray(actions)
-
-    def _staged_actions(self, actions):
-        # host actions -> pinned staging -> the device pairs the kernel consumes as they lie
-        if self._act_pinned is None:
-            self._act_pinned = torch.empty((self.num_envs, 2), dtype=torch.int32, pin_memory=True)
-        np.copyto(self._act_pinned.numpy(), actions.reshape(self.num_envs, 2), casting="unsafe")
-        ego_pairs = self._staged_pairs()
-        ego_pairs.copy_(self._act_pinned, non_blocking=True)
-        return ego_pairs
-
-    def _mapped_step_async(self, actions):
-        """host_io="mapped": everything of a step that can be started -- the actions into mapped
-        memory, the fused step, the pack into mapped memory, the event."""
-        if self._inflight is not None:
-            raise RuntimeError("step_async called again before step_wait")
-        b, n = self._b, self.num_envs
-        actions = np.asarray(actions)
-        f = self._fast
-        if f is None:
-            f = self._fast = self._fast_plan()
-        if f:
-            # the single-launch step reads the ego's pairs where the host wrote them: no staging copy
-            if self._act_mapped is None:
-                self._act_mapped = MappedBuffer(_lib.load(lib="hostio"), b._dev_index, n * 2 * 4)
-                self._act_mapped_np = self._act_mapped.view().view(np.int32).reshape(n, 2)
-            np.copyto(self._act_mapped_np, actions.reshape(n, 2), casting="unsafe")
-            _, rew, done = self._fast_step(f, self._act_mapped.dev, False)
-        else:
-            _, rew, done = self.step_tensors(self._staged_actions(actions))
-        self._mapped_pack()
-        self._inflight = (rew, done)
+        self._transport().start(actions)
 
     def step_wait(self):
-        if self._host_io == "mapped":
-            if self._inflight is None:
-                raise RuntimeError("step_wait without step_async")
-            (rew, done), self._inflight = self._inflight, None
-            obs_np, rew_np, done_i32 = self._mapped_wait(rew, done)
-        else:
-            _, rew, done = self.step_tensors(self._staged_actions(self._pending))
-            obs_np, rew_np, done_i32 = self._host_step(rew, done)
+        obs_np, rew_np, done_i32, stats = self._transport().finish()
         done_np = done_i32.astype(bool)
         infos = self._infos                       # the same list every step (as DummyVecEnv's buf_infos)
         for i in self._dirty:
@@ -683,7 +523,7 @@ class OvercookedVecEnv(_VecEnvBase):
             if self.track_episode_stats:
                 # after a step that returned done the kernel's rows hold the finished episode's
                 # totals; they crossed PCIe with the observation (oc_pack_host)
-                ret, ln = self._host_stats
+                ret, ln = stats
             for i in idx:
                 if self.track_episode_stats:
                     infos[i]["episode"] = {"r": float(ret[i]), "l": int(ln[i])}     # Monitor-style
@@ -692,9 +532,8 @@ class OvercookedVecEnv(_VecEnvBase):
         return obs_np, rew_np, done_np, list(infos)   # shallow copy: holders keep their dicts
 
     def close(self):
-        if self._inflight is not None:      # host_io="mapped": a step nobody waited for ends first
-            self._mapped_wait()
-            self._inflight = None
+        if self._io is not None:            # (a started step nobody waited for ends first)
+            self._io.close()
 
     def seed(self, seed=None):
         return [seed] * self.num_envs

@@ -63,12 +63,13 @@ def test_seed_helper_returns_the_bits_of_the_expression_it_replaced(seed, shape)
 
 
 def test_vec_env_still_exports_every_name_that_moved():
-    from gym_comm_amd import partners, rollout, vec_env
+    from gym_comm_amd import hostio, learner, partners, rollout, vec_env
     home = {"ObsView": vec_env, "SPACE_DTYPE": vec_env, "ClosedLoop": vec_env, "OvercookedVecEnv": vec_env,
             "BatchEpisodeRecorder": vec_env, "RolloutSink": rollout, "RandomPartner": partners,
             "MLPPolicy": partners, "TorchPolicyPartner": partners, "RecurrentPolicyPartner": partners,
-            "FusedMLPPartner": partners}
-    assert len(home) == 11
+            "FusedMLPPartner": partners, "FusedActorCriticPartner": partners, "MLPActorCritic": partners,
+            "PPOLearner": learner, "MappedBuffer": hostio}
+    assert len(home) == 15
     for name, mod in home.items():
         assert getattr(vec_env, name) is getattr(mod, name), name
         if isinstance(getattr(mod, name), type):

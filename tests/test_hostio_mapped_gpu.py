@@ -24,7 +24,7 @@ def _lib_hostio():
 
 
 def _salad_widths():
-    """The plan ``OvercookedVecEnv._host_plan`` makes for open-divider_salad with 3 comm channels."""
+    """The plan ``hostio.pack_plan`` makes for open-divider_salad with 3 comm channels, restated."""
     from gym_comm_amd import compiler
     from gym_comm_amd.batched import obs_layout
     from gym_comm_amd.vec_env import SPACE_DTYPE
@@ -201,8 +201,8 @@ def test_mapped_env_returns_what_the_copying_env_returns():
     for x, xs, s, ss in kept:               # fresh arrays stay what they were
         assert np.array_equal(x, xs) and np.array_equal(s, ss)
     # the single-launch path was taken, and its actions came from mapped memory
-    assert vm._fast and vr._fast and isinstance(vm._act_mapped, MappedBuffer)
-    assert vc._act_mapped is None
+    assert vm._fast and vr._fast and isinstance(vm._io.act, MappedBuffer)
+    assert vc._io.act is None
     # the mapped memory outlives the env while an array of it is alive, and goes with the last one
     owner = weakref.ref(_owner(orr["is_hidden"]))
     want = orr["is_hidden"].copy()
@@ -240,7 +240,7 @@ def test_mapped_env_on_the_slow_path_with_terminal_observations():
                 for key in tc:
                     assert tc[key].dtype == tm[key].dtype and np.array_equal(tc[key], tm[key]), (k, i, key)
                 terminals += 1
-    assert terminals >= 2 * n and vm._fast is False and vm._act_mapped is None
+    assert terminals >= 2 * n and vm._fast is False and vm._io.act is None
 
 
 def test_step_async_and_step_wait_keep_their_protocol():

@@ -12,8 +12,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 
 from aux_kernel_rates import timed
-from gym_comm_amd import _lib
-from gym_comm_amd.vec_env import MappedBuffer, OvercookedVecEnv
+from gym_comm_amd.hostio import HostCopy, MappedBuffer
+from gym_comm_amd.vec_env import OvercookedVecEnv
 
 
 def main():
@@ -23,20 +23,13 @@ def main():
                               communication_on=True, ego_led=False, fow_radius=2)
         venv = OvercookedVecEnv(arg, n, seed=1)
         venv.reset_tensors()
-        b, hp = venv._b, venv._host_plan()
-        L, w = hp["L"], hp["width"]
-        total = hp["dev"].numel()
-        mapped = MappedBuffer(L, b._dev_index, total)
-
-        def pack(name, out):
-            _lib.call(L, name, b._dev_index, b.obs[0].data_ptr(), hp["ot"], b.F, hp["plan"].data_ptr(), w[0], w[1], w[2],
-                      b.timestep.data_ptr(), b.shaped_reward.data_ptr(), b.ep_return.data_ptr(), b.done.data_ptr(),
-                      b.ep_length.data_ptr(), out, n)
-
-        dev = hp["dev"].data_ptr()
-        rows = [("oc_pack_host -> device", lambda: pack("oc_pack_host", dev)),
-                ("oc_pack_host_tiled -> device", lambda: pack("oc_pack_host_tiled", dev)),
-                ("oc_pack_host_tiled -> host-mapped", lambda: pack("oc_pack_host_tiled", mapped.dev))]
+        io = HostCopy(venv)             # the env's own plan and pack launch (episode statistics on)
+        total = io.plan.total
+        mapped = MappedBuffer(io.L, venv._b._dev_index, total)
+        dev = io.dev.data_ptr()
+        rows = [("oc_pack_host -> device", lambda: io.pack("oc_pack_host", dev)),
+                ("oc_pack_host_tiled -> device", lambda: io.pack("oc_pack_host_tiled", dev)),
+                ("oc_pack_host_tiled -> host-mapped", lambda: io.pack("oc_pack_host_tiled", mapped.dev))]
         for rnd in (1, 2):
             out = ["n = %d, %d bytes per step, pass %d:" % (n, total, rnd)]
             for label, fn in rows:
