@@ -136,6 +136,7 @@ def _libs_table():
             "oc_policy_pack_b2v": (cint, [fp, fp, fp, fp, i32, fp]),
             "oc_policy_mlp_ac": (cint, [P(PolicyAcPlayer), i32, vp, i32, i32, i32, i64, vp]),
             # the PPO update of the actor-critic form
+            "oc_policy_pack_w2t": (cint, [fp, fp, i32, fp]),
             "oc_policy_ppo_plan": (cint, [i32, i32, i32, i32, _I32P]),
             "oc_policy_ppo_update": (cint, [P(PpoCfg), vp, i32, vp]),
             "oc_policy_ppo_grad": (cint, [P(PpoCfg), vp, i32, vp]),

@@ -35,7 +35,8 @@ LIBS = {
     # the stepper's specialised builds neither contain nor depend on it
     # (oc_policy_ppo.hip: the PPO update, a second translation unit and code object of the same library)
     "policy": Lib(["oc_policy.hip", "oc_policy_ppo.hip"], ["oc_policy.h"],
-                  ["oc_policy_device.h", "oc_policy_ac_device.h", "oc_policy_ppo_device.h"],
+                  ["oc_policy_device.h", "oc_policy_ac_device.h", "oc_policy_ppo_device.h", "oc_policy_layout.h",
+                   "oc_policy_fail.h"],
                   _PLAIN_FLAGS,
                   os.path.join(CSRC, "liboc_policy.so")),
     # the host-I/O library (include/oc_hostio.h): the numpy boundary's pack-for-PCIe kernel

@@ -3,20 +3,12 @@
 // unit of its own: oc_policy.hip and its code object stay as they were.  gfx950 only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/oc_policy.h"
+#include "oc_policy_fail.h"
 #include "oc_policy_ppo_device.h"
 
-namespace ocpol {
-int host_fail(const char *msg);   // oc_policy.hip: sets what oc_policy_last_error() returns, returns -1
-}
-
-namespace {
 using namespace ocpol;
-thread_local char g_msg[256];
-int fail(const char *msg) { return host_fail(msg); }
-}  // namespace
 
 extern "C" {
 
@@ -38,27 +30,16 @@ int oc_policy_ppo_plan(int32_t F, int32_t C, int32_t B, int32_t max_groups, int3
 namespace {
 int ppo_launch(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t B, void *stream, bool apply) {
   int32_t plan[4];
-  if (!c || !idx) {
-    snprintf(g_msg, sizeof(g_msg), "%s: bad argument (cfg, idx)", who);
-    return fail(g_msg);
-  }
-  if (oc_policy_ppo_plan(c->F, c->C, B, c->max_groups, plan) != 0) {
-    snprintf(g_msg, sizeof(g_msg), "%s: bad argument (1 <= F, F + 2 <= 48, 1 <= C <= 16, B >= 2, max_groups >= 0)", who);
-    return fail(g_msg);
-  }
-  if (c->obs_type < 0 || c->obs_type > 2 || c->T < 1 || c->n < 1 || (int64_t)c->T * c->n >= ((int64_t)1 << 31)) {
-    snprintf(g_msg, sizeof(g_msg), "%s: bad argument (obs_type 0..2, T >= 1, n >= 1, T * n must stay below 2^31)", who);
-    return fail(g_msg);
-  }
+  if (!c || !idx) return fail("%s: bad argument (cfg, idx)", who);
+  if (oc_policy_ppo_plan(c->F, c->C, B, c->max_groups, plan) != 0)
+    return fail("%s: bad argument (1 <= F, F + 2 <= 48, 1 <= C <= 16, B >= 2, max_groups >= 0)", who);
+  if (c->obs_type < 0 || c->obs_type > 2 || c->T < 1 || c->n < 1 || (int64_t)c->T * c->n >= ((int64_t)1 << 31))
+    return fail("%s: bad argument (obs_type 0..2, T >= 1, n >= 1, T * n must stay below 2^31)", who);
   if (!c->obs || !c->timestep || !c->actions || !c->log_probs || !c->advantages || !c->returns || !c->w1 || !c->w2 ||
-      !c->b2 || !c->w2t || !c->grad || !c->scratch || !c->stats || !c->hyper) {
-    snprintf(g_msg, sizeof(g_msg), "%s: a NULL pointer among the rollout tensors, packed weights, grad, scratch, stats, hyper", who);
-    return fail(g_msg);
-  }
-  if (apply && (!c->p_w1 || !c->p_wt || !c->p_b1 || !c->p_w2 || !c->p_b2 || !c->p_wv || !c->p_bv || !c->m || !c->v || !c->step)) {
-    snprintf(g_msg, sizeof(g_msg), "%s: a NULL pointer among the master weights, m, v, step", who);
-    return fail(g_msg);
-  }
+      !c->b2 || !c->w2t || !c->grad || !c->scratch || !c->stats || !c->hyper)
+    return fail("%s: a NULL pointer among the rollout tensors, packed weights, grad, scratch, stats, hyper", who);
+  if (apply && (!c->p_w1 || !c->p_wt || !c->p_b1 || !c->p_w2 || !c->p_b2 || !c->p_wv || !c->p_bv || !c->m || !c->v || !c->step))
+    return fail("%s: a NULL pointer among the master weights, m, v, step", who);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_ppo_adv, dim3(1), dim3(PPO_FINISH_THREADS), 0, st, c->advantages, idx, (int)B, c->stats);
   const dim3 g((unsigned)plan[0]), b(64 * PPO_WAVES);
@@ -69,8 +50,7 @@ int ppo_launch(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t
   else hipLaunchKernelGGL((k_ppo_finish<false>), dim3(1), dim3(PPO_FINISH_THREADS), 0, st, *c, (int)B, (int)plan[0], (const float *)c->scratch);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    snprintf(g_msg, sizeof(g_msg), "%s: kernel launch: %s", who, hipGetErrorString(e));
-    fail(g_msg);
+    fail("%s: kernel launch: %s", who, hipGetErrorString(e));
     return (int)e;
   }
   return 0;

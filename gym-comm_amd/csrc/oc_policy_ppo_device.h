@@ -28,11 +28,12 @@
 //   k_ppo_finish   one workgroup: partials summed over g ascending, one thread per parameter; the
 //                  squared norm in double, in a fixed order; clip; statistics; and (APPLY) Adam on
 //                  the fp32 master weights and the repack of every fragment image on the device,
-//                  bit for bit oc_policy_pack_w1 / _w2v / _b2v's.
+//                  through the host packers' own maps (oc_policy_layout.h).
 #ifndef OC_POLICY_PPO_DEVICE_H
 #define OC_POLICY_PPO_DEVICE_H
 #include "../../include/oc_policy.h"
 #include "oc_policy_ac_device.h"
+#include "oc_policy_layout.h"
 
 namespace ocpol {
 
@@ -42,37 +43,6 @@ constexpr int PPO_ROWS = 112;         // phase A: dlogits 32 + h 64; phase B: dp
 constexpr int PPO_SUMS = 8;           // loss sums a workgroup appends to its partial gradient
 constexpr int PPO_FINISH_THREADS = 1024;
 constexpr int PPO_MAX_P = 5 * PPO_FINISH_THREADS;   // >= 64 * 46 + 128 + 20 * 64 + 20 + 65 = 4437
-
-// which logit (0..3 move, 4 + c comm) lives in row o of the second product, or -1 (oc_policy.hip)
-__host__ __device__ inline int ppo_logit_of_row(int o, int C) {
-  if (o < 4) return o;
-  if (((o - 4) & 7) < 4) {
-    const int c = ((o - 4) & 3) + 4 * ((o - 4) >> 3);
-    if (c < C) return 4 + c;
-  }
-  return -1;
-}
-
-// offsets of the seven tensors in the flat parameter vector [P]
-struct PpoLayout {
-  int F, C, wt, b1, w2, b2, wv, bv, P;
-  __host__ __device__ PpoLayout(int F_, int C_) : F(F_), C(C_) {
-    wt = 64 * F, b1 = wt + 64, w2 = b1 + 64, b2 = w2 + (4 + C) * 64, wv = b2 + 4 + C, bv = wv + 64, P = bv + 1;
-  }
-  // element (hidden, feature) of the first layer's augmented gradient
-  __host__ __device__ int first(int hid, int f) const {
-    return f < F ? hid * F + f : f == F ? wt + hid : f == F + 1 ? b1 + hid : -1;
-  }
-  // element (row of the second product, hidden)
-  __host__ __device__ int second(int row, int hid) const {
-    const int lg = ppo_logit_of_row(row, C);
-    return lg >= 0 ? w2 + lg * 64 + hid : row == 8 ? wv + hid : -1;
-  }
-  __host__ __device__ int bias(int row) const {
-    const int lg = ppo_logit_of_row(row, C);
-    return lg >= 0 ? b2 + lg : row == 8 ? bv : -1;
-  }
-};
 
 __device__ __forceinline__ float *ppo_param(const oc_ppo_cfg &p, const PpoLayout &lay, int pi) {
   if (pi < lay.wt) return p.p_w1 + pi;
@@ -84,6 +54,7 @@ __device__ __forceinline__ float *ppo_param(const oc_ppo_cfg &p, const PpoLayout
   return p.p_bv;
 }
 
+// obs_at with a 64-bit index: T * F * n exceeds 32 bits, and obs_at is 32-bit on purpose (oc_policy_device.h)
 template <int OT>
 __device__ __forceinline__ float ppo_obs_at(const void *obs, size_t idx) {
   if (OT == 1) return (float)((const int8_t *)obs)[idx];
@@ -128,7 +99,7 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
   __shared__ float lds[PPO_WAVES * PPO_ROWS * PPO_STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
   float *L = lds + wv * (PPO_ROWS * PPO_STRIDE);
-  const int F = p.F, C = p.C, ks = (F + 2 + 15) / 16;
+  const int F = p.F, C = p.C, ks = ksteps(F);
   const size_t n = (size_t)p.n;
   const uint32_t n32 = (uint32_t)p.n;
   const int W = (int)gridDim.x * PPO_WAVES, gw = (int)blockIdx.x * PPO_WAVES + wv;
@@ -281,7 +252,7 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
     // ---- phase A: dlogits and h through LDS; dW2 and db2 ----
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-      const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
+      const int row = acc_row(q, h);
       L[row * PPO_STRIDE + r] = d[q];
       L[(32 + row) * PPO_STRIDE + r] = 1.0f - 2.0f * rv[0][q];
       L[(64 + row) * PPO_STRIDE + r] = 1.0f - 2.0f * rv[1][q];
@@ -301,7 +272,7 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
     // dh is in units of the folded weights: W2 = W2' / (-2 log2 e), so dpre = (-ln 2 / 2) dh 4 r (1 - r)
 #pragma unroll
     for (int q = 0; q < 16; q++) {
-      const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
+      const int row = acc_row(q, h);
       L[row * PPO_STRIDE + r] = (-2.0f * K_LN2 * dh0[q]) * (rv[0][q] * (1.0f - rv[0][q]));
       L[(32 + row) * PPO_STRIDE + r] = (-2.0f * K_LN2 * dh1[q]) * (rv[1][q] * (1.0f - rv[1][q]));
     }
@@ -340,7 +311,7 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
     for (int u = 0; u < 4; u++) {
       const int el = tid + 256 * u, q = el >> 6, ln = el & 63;
       const float s = ((lds[el] + lds[1024 + el]) + lds[2048 + el]) + lds[3072 + el];
-      const int pi = index_of((q & 3) + 8 * (q >> 2) + 4 * (ln >> 5), ln & 31);
+      const int pi = index_of(acc_row(q, ln >> 5), ln & 31);
       if (pi >= 0) mine[pi] = s;
     }
   };
@@ -372,16 +343,12 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
 }
 
 // ---- c, d. reduce, clip, statistics; Adam and the repack ---------------------------------------
-__device__ __forceinline__ float ppo_folded(float w, float scale) {   // the fp16 value a product multiplies by
-  return (float)(_Float16)(scale * w);
-}
-
 template <bool APPLY>
 __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const oc_ppo_cfg p, const int B, const int G,
                                                                   const float *part) {
   __shared__ double red[PPO_FINISH_THREADS];
   __shared__ float neww[APPLY ? PPO_MAX_P : 1];
-  __shared__ float rowsum[OC_POLICY_MAX_COMM + 5];
+  __shared__ float start[OC_POLICY_MAX_COMM + 5];   // b2's value per logit row, then the value head's
   const int tid = threadIdx.x, F = p.F, C = p.C;
   const PpoLayout lay(F, C);
   const size_t stride = (size_t)(lay.P + PPO_SUMS);
@@ -439,44 +406,32 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const oc_ppo_
     }
     __syncthreads();
     if (tid == 0) p.step[0] = step;
-    // the repack, from the new weights in LDS: oc_policy_pack_w1 / _w2v / _b2v's values, operation for
-    // operation (the products in fp32, rounded to fp16; the row sums over the ROUNDED weights, j ascending)
-    const float s1 = 2.0f * K_LOG2E, s2 = -2.0f * K_LOG2E;
+    // the repack, from the new weights in LDS: the host packers' values through the same maps and the
+    // same fold (oc_policy_layout.h), looked up in the flat parameter vector
     const int rows2 = 4 + C;                     // logit rows; row `rows2` stands for the value head
-    if (tid <= rows2) {
-      const float *wrow = neww + (tid < rows2 ? lay.w2 + tid * 64 : lay.wv);
-      float sum = 0.0f;
-      for (int j = 0; j < OC_POLICY_HIDDEN; j++) sum += ppo_folded(wrow[j], s2);
-      rowsum[tid] = sum;
-    }
+    if (tid <= rows2)
+      start[tid] = b2_start(neww[tid < rows2 ? lay.b2 + tid : lay.bv], neww + (tid < rows2 ? lay.w2 + tid * HIDDEN : lay.wv));
     __syncthreads();
-    const int ks = (F + 2 + 15) / 16;
+    const int ks = ksteps(F);
     _Float16 *o1 = (_Float16 *)p.w1, *o2 = (_Float16 *)p.w2;
-    for (int el = tid; el < 2 * ks * 64 * 8; el += PPO_FINISH_THREADS) {
-      const int j = el & 7, l = (el >> 3) & 63, ms = el >> 9, s = ms % ks, m = ms / ks;
-      const int pi = lay.first(32 * m + (l & 31), 16 * s + 8 * (l >> 5) + j);
-      o1[el] = (_Float16)(s1 * (pi >= 0 ? neww[pi] : 0.0f));
+    for (int el = tid; el < w1_elems(ks); el += PPO_FINISH_THREADS) {
+      const HidK s = w1_source(el, ks);
+      const int pi = lay.first(s.hid, s.k);
+      o1[el] = fold(pi >= 0 ? neww[pi] : 0.0f, FOLD_W1);
     }
-    for (int el = tid; el < 4 * 64 * 8; el += PPO_FINISH_THREADS) {
-      const int j = el & 7, l = (el >> 3) & 63, s = el >> 9;
-      const int pi = lay.second(l & 31, 16 * s + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3));
-      o2[el] = pi >= 0 ? (_Float16)(s2 * neww[pi]) : (_Float16)0.0f;
+    for (int el = tid; el < W2_ELEMS; el += PPO_FINISH_THREADS) {
+      const RowHid s = w2_source(el);
+      const int pi = lay.second(s.row, s.hid);
+      o2[el] = pi >= 0 ? fold(neww[pi], FOLD_W2) : (_Float16)0.0f;
     }
-    for (int el = tid; el < 64 * 16; el += PPO_FINISH_THREADS) {
-      const int q = el & 15, l = el >> 4, row = (q & 3) + 8 * (q >> 2) + 4 * (l >> 5);
-      const int pi = lay.bias(row);
-      float v = 0.0f;
-      if (pi >= 0) {
-#pragma clang fp contract(off)
-        v = K_LOG2E * neww[pi] - 0.5f * rowsum[pi - lay.b2 < rows2 ? pi - lay.b2 : rows2];
-      }
-      p.b2[el] = v;
+    for (int el = tid; el < B2_ELEMS; el += PPO_FINISH_THREADS) {
+      const int pi = lay.bias(b2_row(el));
+      p.b2[el] = pi >= 0 ? start[pi < lay.wv ? pi - lay.b2 : rows2] : 0.0f;
     }
-    // the learner's own image: W2' transposed, k-permuted to the accumulator order of dlogits, fp32
-    for (int el = tid; el < 2 * 16 * 64; el += PPO_FINISH_THREADS) {
-      const int l = el & 63, t = (el >> 6) & 15, m = el >> 10;
-      const int pi = lay.second((t & 3) + 8 * (t >> 2) + 4 * (l >> 5), 32 * m + (l & 31));
-      p.w2t[el] = pi >= 0 ? ppo_folded(neww[pi], s2) : 0.0f;
+    for (int el = tid; el < W2T_ELEMS; el += PPO_FINISH_THREADS) {
+      const RowHid s = w2t_source(el);
+      const int pi = lay.second(s.row, s.hid);
+      p.w2t[el] = pi >= 0 ? (float)fold(neww[pi], FOLD_W2) : 0.0f;
     }
   }
 }

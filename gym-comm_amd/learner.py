@@ -2,12 +2,11 @@
 launches per minibatch (include/oc_policy.h: ``oc_policy_ppo_update``) -- see ``vec_env`` for the overview."""
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib
 from .batched import OBS_TYPE
-from .partners import FusedActorCriticPartner
+from .partners import FusedActorCriticPartner, pack_w2t
 
 STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm",
          "adv_mean", "adv_std", "bad", "loss")
@@ -58,40 +57,16 @@ class PPOLearner:
         self.betas, self.eps, self.max_groups = (float(betas[0]), float(betas[1])), float(eps), int(max_groups)
         self._scratch, self._retired = None, []
         self._w2t = z(2 * 16 * 64)
-        self._w2t_src = self._w2t_index()
         self._cfgs = {}
         self.lp_out = self.v_out = None          # set to float [B] tensors to receive the forward (tests)
         self.refresh()
 
-    # ---- the learner's own packed image ----
-    def _w2t_index(self):
-        """For element (m, t, l) of ``w2t``: the index into [w2; wv] flattened, or -1."""
-        src = np.full((2, 16, 64), -1, np.int64)
-        for m in range(2):
-            for t in range(16):
-                for lane in range(64):
-                    row, hid = (t & 3) + 8 * (t >> 2) + 4 * (lane >> 5), 32 * m + (lane & 31)
-                    if row < 4:
-                        src[m, t, lane] = row * 64 + hid
-                    elif row == 8:
-                        src[m, t, lane] = (4 + self.C) * 64 + hid
-                    elif ((row - 4) & 7) < 4:
-                        c = ((row - 4) & 3) + 4 * ((row - 4) >> 3)
-                        if c < self.C:
-                            src[m, t, lane] = (4 + c) * 64 + hid
-        return torch.from_numpy(src.reshape(-1)).to(self.device)
-
     def refresh(self):
         """After the module's weights were changed from OUTSIDE (a checkpoint loaded, say): repack the
-        seat's fragments (``seat.refresh()``) and the learner's transposed image.  ``update`` keeps both
-        current itself."""
+        seat's fragments (``seat.refresh()``) and the learner's transposed image, in place (a captured
+        graph keeps the address).  ``update`` keeps both current itself."""
         self.seat.refresh()
-        with torch.no_grad():
-            scale = float(np.float32(-2) * np.float32(1.4426950408889634))
-            rows = torch.cat([self.policy.w2.reshape(-1), self.policy.wv.reshape(-1)])
-            folded = (rows * scale).to(torch.float16).to(torch.float32)
-            src = self._w2t_src
-            self._w2t.copy_(torch.where(src >= 0, folded[src.clamp(min=0)], torch.zeros((), device=self.device)))
+        self._w2t.copy_(torch.from_numpy(pack_w2t(self._L, self.policy).reshape(-1)))
 
     # ---- hyper-parameters read on the device ----
     def set_lr(self, lr):

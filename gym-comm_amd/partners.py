@@ -270,30 +270,45 @@ class RecurrentPolicyPartner(_RecordingSeat):
             self.sink.set_state(st[4])
 
 
+def _f32(t):
+    return np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+
+
+def _fp(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
 def pack_fragments(L, policy, value_head=False):
     """The module's current weights in MFMA fragment order (include/oc_policy.h: the packers of ``L``,
     the policy library): numpy ``(o1, o2, ob)`` = first layer (timestep column and bias folded in),
     second layer, second bias.  ``value_head``: an ``MLPActorCritic``'s value row rides in ``o2`` / ``ob``
     (``oc_policy_pack_w2v`` / ``_b2v``).  Host code only: no device call."""
-    f32 = lambda t: np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
-    fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
     F, C = int(policy.w1.shape[1]), int(policy.C)
-    w1, wt, b1, w2, b2 = (f32(t) for t in (policy.w1, policy.wt, policy.b1, policy.w2, policy.b2))
+    w1, wt, b1, w2, b2 = (_f32(t) for t in (policy.w1, policy.wt, policy.b1, policy.w2, policy.b2))
     o1 = np.zeros((2, L.oc_policy_ksteps(F), 64, 8), np.uint16)
     o2 = np.zeros((4, 64, 8), np.uint16)
     ob = np.zeros((64, 16), np.float32)
     vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    done = [(L.oc_policy_pack_w1(fp(w1), fp(wt.reshape(-1)), fp(b1.reshape(-1)), F, vp(o1)), "oc_policy_pack_w1")]
+    done = [(L.oc_policy_pack_w1(_fp(w1), _fp(wt.reshape(-1)), _fp(b1.reshape(-1)), F, vp(o1)), "oc_policy_pack_w1")]
     if value_head:
-        wv, bv = f32(policy.wv).reshape(-1), f32(policy.bv).reshape(-1)
-        done += [(L.oc_policy_pack_w2v(fp(w2), fp(wv), C, vp(o2)), "oc_policy_pack_w2v"),
-                 (L.oc_policy_pack_b2v(fp(b2.reshape(-1)), fp(w2), fp(bv), fp(wv), C, fp(ob)), "oc_policy_pack_b2v")]
+        wv, bv = _f32(policy.wv).reshape(-1), _f32(policy.bv).reshape(-1)
+        done += [(L.oc_policy_pack_w2v(_fp(w2), _fp(wv), C, vp(o2)), "oc_policy_pack_w2v"),
+                 (L.oc_policy_pack_b2v(_fp(b2.reshape(-1)), _fp(w2), _fp(bv), _fp(wv), C, _fp(ob)), "oc_policy_pack_b2v")]
     else:
-        done += [(L.oc_policy_pack_w2(fp(w2), C, vp(o2)), "oc_policy_pack_w2"),
-                 (L.oc_policy_pack_b2(fp(b2.reshape(-1)), fp(w2), C, fp(ob)), "oc_policy_pack_b2")]
+        done += [(L.oc_policy_pack_w2(_fp(w2), C, vp(o2)), "oc_policy_pack_w2"),
+                 (L.oc_policy_pack_b2(_fp(b2.reshape(-1)), _fp(w2), C, _fp(ob)), "oc_policy_pack_b2")]
     for rc, what in done:
         _lib.check(rc, what, L)
     return o1, o2, ob
+
+
+def pack_w2t(L, policy):
+    """A learner's own image of an ``MLPActorCritic``'s second layer (include/oc_policy.h: ``w2t``): numpy
+    float32 [2][16][64], the folded weights transposed.  Host code only, as ``pack_fragments``."""
+    out = np.zeros((2, 16, 64), np.float32)
+    rc = L.oc_policy_pack_w2t(_fp(_f32(policy.w2)), _fp(_f32(policy.wv).reshape(-1)), int(policy.C), _fp(out))
+    _lib.check(rc, "oc_policy_pack_w2t", L)
+    return out
 
 
 class _FusedSeat:

@@ -173,7 +173,8 @@ OC_API int oc_policy_mlp_ac(const oc_policy_ac_player *players, int32_t num_play
  * oc_policy_pack_w1 / _w2v / _b2v produce on the host from the same fp32 weights, and so is `w2t`,
  * the learner's own image: float [2][16][64], element (m, t, l) = the fp16 value of -2 log2(e) W2row
  * [(t & 3) + 8 (t >> 2) + 4 (l >> 5)][32 m + (l & 31)] (the value head is row 8) -- W2 transposed and
- * k-permuted to the order in which d logits sit in the accumulators.
+ * k-permuted to the order in which d logits sit in the accumulators.  oc_policy_pack_w2t (below)
+ * produces it on the host, for a learner's first image.
  *
  * stats, float [10], written on the device and never read by the library except [6], [7] within
  * one call: policy_loss, value_loss, entropy_loss, approx_kl = mean(old_lp - lp), clip_fraction
@@ -206,7 +207,10 @@ typedef struct {
   float *lp_out, *v_out;      /* optional out, float [B]: the forward's log_prob and value */
 } oc_ppo_cfg;
 
-/* No device work: plan = (workgroups G of the gradient kernel, tiles of 32 samples per wave, P,
+/* Host-side packing of `w2t` (above): w2 [4 + C][64], wv [64]  ->  out fp32 [2][16][64]. */
+OC_API int oc_policy_pack_w2t(const float *w2, const float *wv, int32_t C, float *out);
+
+/* No device work: plan =(workgroups G of the gradient kernel, tiles of 32 samples per wave, P,
  * floats of scratch).  Wave w of the 4 G takes tiles w, w + 4 G, ...: no workgroup is empty. */
 OC_API int oc_policy_ppo_plan(int32_t F, int32_t C, int32_t B, int32_t max_groups, int32_t *plan);
 

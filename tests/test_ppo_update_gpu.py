@@ -207,6 +207,11 @@ def test_three_updates_adam_and_the_repacked_fragments():
         lp_twin, v_twin = twin.score(*_probe_args(e, probe))
         assert torch.equal(_bits(lp_after), _bits(lp_twin)) and torch.equal(_bits(v_after), _bits(v_twin))
         assert not torch.equal(_bits(lp_after), _bits(lp_before))
+    # an explicit refresh() repacks on the host, in place: the same address (captured graphs keep it)
+    # and, from the weights the updates left, the same bits
+    ptr, before = ln._w2t.data_ptr(), _bits(ln._w2t).clone()
+    ln.refresh()
+    assert ln._w2t.data_ptr() == ptr and torch.equal(_bits(ln._w2t), before)
 
 
 def _probe_args(e, idx):
