@@ -67,6 +67,16 @@ class PpoCfg(ctypes.Structure):
                [("max_groups", ctypes.c_int32), ("lp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
 
 
+class PpoTrain(ctypes.Structure):
+    """oc_ppo_train (include/oc_policy.h): the train sequence's device state."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("values", "hyper_ext", "ctl", "acc")]
+
+
+# oc_ppo_train's word indices (OC_PPO_CTL_* / OC_PPO_ACC_* of include/oc_policy.h)
+PPO_CTL = {"stop": 0, "epoch": 1, "updates": 2, "epochs": 3, "error": 4, "words": 8}
+PPO_ACC = {"epoch_kl": 0, "epoch_count": 1, "sums": 2, "words": 8}
+
+
 class RolloutBuf(ctypes.Structure):
     """oc_rollout_buf (include/oc_rollout.h)."""
     _fields_ = [(name, ctypes.c_void_p) for name in
@@ -88,7 +98,7 @@ Lib = collections.namedtuple("Lib", "env abi_fn abi_version last_error protos")
 
 def _libs_table():
     cint, cstr, vp, fp = ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)
-    i32, i64, P = ctypes.c_int32, ctypes.c_int64, ctypes.POINTER
+    i32, i64, u32, P = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.POINTER
     bp = P(RolloutBuf)
     multi_step = [vp, vp, vp, vp, P(WrapCfg), vp, vp, vp, vp, vp, i32, vp, vp, vp, P(StepOpts), i64]
     return {
@@ -140,6 +150,11 @@ def _libs_table():
             "oc_policy_ppo_plan": (cint, [i32, i32, i32, i32, _I32P]),
             "oc_policy_ppo_update": (cint, [P(PpoCfg), vp, i32, vp]),
             "oc_policy_ppo_grad": (cint, [P(PpoCfg), vp, i32, vp]),
+            # the train sequence: device shuffle, KL stop, value clipping, accumulated statistics
+            "oc_policy_ppo_perm_host": (cint, [u32, i32, i32, _I32P]),
+            "oc_policy_ppo_train_begin": (cint, [P(PpoTrain), vp]),
+            "oc_policy_ppo_epoch_begin": (cint, [P(PpoTrain), vp, i32, i32, u32, vp]),
+            "oc_policy_ppo_train_step": (cint, [P(PpoCfg), P(PpoTrain), vp, i32, vp]),
         }),
         "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
             "oc_hostio_abi_version": (cint, None),

@@ -1,6 +1,7 @@
 // oc_policy_ppo.hip -- the PPO update's entry points of liboc_policy.so (include/oc_policy.h:
 // oc_policy_ppo_plan / _update / _grad); the kernels are in oc_policy_ppo_device.h.  A translation
 // unit of its own: oc_policy.hip and its code object stay as they were.  gfx950 only.
+// (The train sequence's entry points and its variants of these kernels: oc_policy_train.hip.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,9 +28,8 @@ int oc_policy_ppo_plan(int32_t F, int32_t C, int32_t B, int32_t max_groups, int3
 
 }  // extern "C"
 
-namespace {
-int ppo_launch(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t B, void *stream, bool apply) {
-  int32_t plan[4];
+// the checks of one minibatch, for both translation units (declared in oc_policy_ppo_device.h)
+int ocpol::ppo_check(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t B, bool apply, int32_t *plan) {
   if (!c || !idx) return fail("%s: bad argument (cfg, idx)", who);
   if (oc_policy_ppo_plan(c->F, c->C, B, c->max_groups, plan) != 0)
     return fail("%s: bad argument (1 <= F, F + 2 <= 48, 1 <= C <= 16, B >= 2, max_groups >= 0)", who);
@@ -40,20 +40,23 @@ int ppo_launch(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t
     return fail("%s: a NULL pointer among the rollout tensors, packed weights, grad, scratch, stats, hyper", who);
   if (apply && (!c->p_w1 || !c->p_wt || !c->p_b1 || !c->p_w2 || !c->p_b2 || !c->p_wv || !c->p_bv || !c->m || !c->v || !c->step))
     return fail("%s: a NULL pointer among the master weights, m, v, step", who);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_ppo_adv, dim3(1), dim3(PPO_FINISH_THREADS), 0, st, c->advantages, idx, (int)B, c->stats);
-  const dim3 g((unsigned)plan[0]), b(64 * PPO_WAVES);
-  if (c->obs_type == 1) hipLaunchKernelGGL((k_ppo_grad<1>), g, b, 0, st, *c, idx, (int)B, (int)plan[1], c->scratch);
-  else if (c->obs_type == 2) hipLaunchKernelGGL((k_ppo_grad<2>), g, b, 0, st, *c, idx, (int)B, (int)plan[1], c->scratch);
-  else hipLaunchKernelGGL((k_ppo_grad<0>), g, b, 0, st, *c, idx, (int)B, (int)plan[1], c->scratch);
-  if (apply) hipLaunchKernelGGL((k_ppo_finish<true>), dim3(1), dim3(PPO_FINISH_THREADS), 0, st, *c, (int)B, (int)plan[0], (const float *)c->scratch);
-  else hipLaunchKernelGGL((k_ppo_finish<false>), dim3(1), dim3(PPO_FINISH_THREADS), 0, st, *c, (int)B, (int)plan[0], (const float *)c->scratch);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
   return 0;
+}
+
+namespace {
+int ppo_launch(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t B, void *stream, bool apply) {
+  int32_t plan[4];
+  if (ppo_check(who, c, idx, B, apply, plan) != 0) return -1;
+  const PpoArgs<false> a{*c};
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ppo_adv<false>, dim3(1), dim3(PPO_FINISH_THREADS), 0, st, c->advantages, idx, (int)B, AdvOut<false>{c->stats});
+  const dim3 g((unsigned)plan[0]), b(64 * PPO_WAVES);
+  if (c->obs_type == 1) hipLaunchKernelGGL((k_ppo_grad<1>), g, b, 0, st, a, idx, (int)B, (int)plan[1], c->scratch);
+  else if (c->obs_type == 2) hipLaunchKernelGGL((k_ppo_grad<2>), g, b, 0, st, a, idx, (int)B, (int)plan[1], c->scratch);
+  else hipLaunchKernelGGL((k_ppo_grad<0>), g, b, 0, st, a, idx, (int)B, (int)plan[1], c->scratch);
+  if (apply) hipLaunchKernelGGL((k_ppo_finish<true>), dim3(1), dim3(PPO_FINISH_THREADS), 0, st, a, (int)B, (int)plan[0], (const float *)c->scratch);
+  else hipLaunchKernelGGL((k_ppo_finish<false>), dim3(1), dim3(PPO_FINISH_THREADS), 0, st, a, (int)B, (int)plan[0], (const float *)c->scratch);
+  return ppo_launched(who);
 }
 
 }  // namespace

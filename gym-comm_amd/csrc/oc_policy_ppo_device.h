@@ -1,5 +1,8 @@
 // oc_policy_ppo_device.h -- the kernels of the PPO update (include/oc_policy.h: oc_policy_ppo_update,
-// oc_policy_ppo_grad) for the fused actor-critic seat.  Included by oc_policy_ppo.hip only.  gfx950 only.
+// oc_policy_ppo_grad) for the fused actor-critic seat, and -- the same templates with TRAIN = true -- of
+// a step of the train sequence (oc_policy_ppo_train_step).  Included by oc_policy_ppo.hip, which
+// instantiates the TRAIN = false kernels only, and by oc_policy_train.hip, which instantiates the
+// TRAIN = true ones only.  gfx950 only.
 //
 // Three launches per minibatch, all sized by B alone:
 //
@@ -29,10 +32,17 @@
 //                  squared norm in double, in a fixed order; clip; statistics; and (APPLY) Adam on
 //                  the fp32 master weights and the repack of every fragment image on the device,
 //                  through the host packers' own maps (oc_policy_layout.h).
+//
+// TRAIN = true (oc_policy_ppo_train_step): every kernel returns at once, having written nothing, when
+// the train sequence is halted (ctl.stop or ctl.error); k_ppo_grad clips the value prediction around
+// the recorded value where hyper_ext[0] > 0; k_ppo_finish adds the minibatch's statistics to the
+// epoch's and the train's sums.  TRAIN = false takes the arguments, and compiles to the code, it had
+// before the variants existed: PpoArgs<false> and AdvOut<false> add no member.
 #ifndef OC_POLICY_PPO_DEVICE_H
 #define OC_POLICY_PPO_DEVICE_H
 #include "../../include/oc_policy.h"
 #include "oc_policy_ac_device.h"
+#include "oc_policy_fail.h"
 #include "oc_policy_layout.h"
 
 namespace ocpol {
@@ -43,6 +53,28 @@ constexpr int PPO_ROWS = 112;         // phase A: dlogits 32 + h 64; phase B: dp
 constexpr int PPO_SUMS = 8;           // loss sums a workgroup appends to its partial gradient
 constexpr int PPO_FINISH_THREADS = 1024;
 constexpr int PPO_MAX_P = 5 * PPO_FINISH_THREADS;   // >= 64 * 46 + 128 + 20 * 64 + 20 + 65 = 4437
+
+// the kernels' arguments: the update's alone, or with the train sequence's device state behind them
+template <bool TRAIN>
+struct PpoArgs : oc_ppo_cfg {};
+template <>
+struct PpoArgs<true> : oc_ppo_cfg {
+  oc_ppo_train tr;
+};
+template <bool TRAIN>
+struct AdvOut {
+  float *stats;
+};
+template <>
+struct AdvOut<true> {
+  float *stats;
+  const int32_t *ctl;
+};
+
+// a halted train sequence: stopped by the KL rule, or an error word set (oc_policy.h)
+__device__ __forceinline__ bool ppo_halted(const int32_t *ctl) {
+  return (ctl[OC_PPO_CTL_STOP] | ctl[OC_PPO_CTL_ERROR]) != 0;
+}
 
 __device__ __forceinline__ float *ppo_param(const oc_ppo_cfg &p, const PpoLayout &lay, int pi) {
   if (pi < lay.wt) return p.p_w1 + pi;
@@ -76,8 +108,13 @@ __device__ __forceinline__ double ppo_block_sum(double *red, double mine) {
 }
 
 // ---- a. advantage statistics ----------------------------------------------------------------
+template <bool TRAIN = false>
 __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_adv(const float *adv, const int32_t *idx, const int B,
-                                                               float *stats) {
+                                                               const AdvOut<TRAIN> out) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(out.ctl)) return;   // uniform
+  }
+  float *stats = out.stats;
   __shared__ double red[PPO_FINISH_THREADS];
   const int tid = threadIdx.x;
   double s = 0.0;
@@ -93,9 +130,12 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_adv(const float *adv
 }
 
 // ---- b. loss and gradient -------------------------------------------------------------------
-template <int OT>
-__global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p, const int32_t *idx, const int B,
+template <int OT, bool TRAIN = false>
+__global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const PpoArgs<TRAIN> p, const int32_t *idx, const int B,
                                                              const int tpw, float *part) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(p.tr.ctl)) return;   // uniform
+  }
   __shared__ float lds[PPO_WAVES * PPO_ROWS * PPO_STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
   float *L = lds + wv * (PPO_ROWS * PPO_STRIDE);
@@ -106,6 +146,9 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
   const PpoLayout lay(F, C);
   const float mean = p.stats[6], denom = p.stats[7] + 1e-8f, clip = p.hyper[1];
   const float lo = 1.0f - clip, hi = 1.0f + clip;
+  float cvf = 0.0f;                      // clip_range_vf; <= 0 (or NaN): no value clipping
+  if constexpr (TRAIN) cvf = p.tr.hyper_ext[0];
+  const bool vclip = cvf > 0.0f;         // uniform
 
   Weights wt;
   load_weights(wt, p.w1, p.w2, p.b2, lane, ks);
@@ -227,12 +270,23 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
       const float v = glp * ((c == a ? 1.0f : 0.0f) - pr[c]) + p.ent_coef * (pr[c] * (lnp[c] + H));
       d[c] = (ok && c < count) ? v : 0.0f;
     }
-    if (h == 0 && ok) d[4] = 2.0f * p.vf_coef * (val - ret);
+    // value clipping (TRAIN): the prediction moves at most cvf from the recorded value, and the
+    // gradient passes where it has not been cut (the ends included, as torch's clamp backward does)
+    float vp = val;
+    bool vopen = true;
+    if constexpr (TRAIN) {
+      if (vclip) {
+        const float oldv = p.tr.values[smp], dv = val - oldv;
+        vp = oldv + fminf(fmaxf(dv, -cvf), cvf);
+        vopen = dv >= -cvf && dv <= cvf;
+      }
+    }
+    if (h == 0 && ok) d[4] = vopen ? 2.0f * p.vf_coef * (vp - ret) : 0.0f;
     if (ok) {
       s_ent -= H;
       if (h == 0) {
         s_pol -= fminf(t1, t2);
-        s_val += (ret - val) * (ret - val);
+        s_val += (ret - vp) * (ret - vp);
         s_kl += old - lp_sum;
         s_clip += fabsf(ratio - 1.0f) > clip ? 1.0f : 0.0f;
       }
@@ -343,9 +397,12 @@ __global__ void __launch_bounds__(64 * PPO_WAVES) k_ppo_grad(const oc_ppo_cfg p,
 }
 
 // ---- c, d. reduce, clip, statistics; Adam and the repack ---------------------------------------
-template <bool APPLY>
-__global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const oc_ppo_cfg p, const int B, const int G,
+template <bool APPLY, bool TRAIN = false>
+__global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const PpoArgs<TRAIN> p, const int B, const int G,
                                                                   const float *part) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(p.tr.ctl)) return;   // uniform
+  }
   __shared__ double red[PPO_FINISH_THREADS];
   __shared__ float neww[APPLY ? PPO_MAX_P : 1];
   __shared__ float start[OC_POLICY_MAX_COMM + 5];   // b2's value per logit row, then the value head's
@@ -386,6 +443,17 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const oc_ppo_
     p.stats[3] = (float)(s[3] / B), p.stats[4] = (float)(s[4] / B), p.stats[5] = norm;
     p.stats[8] = (float)s[5];
     p.stats[9] = (float)(pol + (double)p.ent_coef * ent + (double)p.vf_coef * val);
+    if constexpr (TRAIN) {
+      // the float values just written, added in double by this one thread: the same sequence of
+      // minibatches gives the same sums, bit for bit
+      double *acc = p.tr.acc;
+      acc[OC_PPO_ACC_EPOCH_KL] += (double)p.stats[3];
+      acc[OC_PPO_ACC_EPOCH_COUNT] += 1.0;
+      acc[OC_PPO_ACC_SUMS + 0] += (double)p.stats[0], acc[OC_PPO_ACC_SUMS + 1] += (double)p.stats[1];
+      acc[OC_PPO_ACC_SUMS + 2] += (double)p.stats[2], acc[OC_PPO_ACC_SUMS + 3] += (double)p.stats[3];
+      acc[OC_PPO_ACC_SUMS + 4] += (double)p.stats[4], acc[OC_PPO_ACC_SUMS + 5] += (double)p.stats[9];
+      p.tr.ctl[OC_PPO_CTL_UPDATES] += 1;
+    }
   }
   if constexpr (APPLY) {
     const int step = p.step[0] + 1;
@@ -434,6 +502,20 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const oc_ppo_
       p.w2t[el] = pi >= 0 ? (float)fold(neww[pi], FOLD_W2) : 0.0f;
     }
   }
+}
+
+// ---- host side, shared by the two units --------------------------------------------------------
+// the checks of one minibatch, made before any device work (oc_policy_ppo.hip); plan as oc_policy_ppo_plan's
+int ppo_check(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t B, bool apply, int32_t *plan);
+
+// after a unit's launches: 0, or the launch error, recorded under the entry point's name
+inline int ppo_launched(const char *who) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    fail("%s: kernel launch: %s", who, hipGetErrorString(e));
+    return (int)e;
+  }
+  return 0;
 }
 
 }  // namespace ocpol

@@ -11,6 +11,7 @@ from .partners import FusedActorCriticPartner, pack_w2t
 STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm",
          "adv_mean", "adv_std", "bad", "loss")
 PARAMS = ("w1", "wt", "b1", "w2", "b2", "wv", "bv")        # the order of the flat gradient [P]
+TRAIN_STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "loss")   # train_stats()
 
 
 class PPOLearner:
@@ -21,10 +22,15 @@ class PPOLearner:
     without a synchronisation, capturable into a graph.  The learner owns Adam's ``m``, ``v`` and step
     counter, the scratch, the statistics and the flat gradient ``grad_flat`` (``grads[name]`` are views of it).
     ``lr`` and ``clip_range`` live in a device tensor (``hyper``): ``set_lr`` / ``set_clip_range`` are
-    device writes, so a schedule needs no new capture."""
+    device writes, so a schedule needs no new capture.
+
+    A whole ``train()`` can run on device-side state as well (``train(shuffle="device")``,
+    ``train_graph``: include/oc_policy.h, the train sequence): the epoch's permutation, stable-baselines3's
+    ``clip_range_vf``, the reference's ``target_kl`` stop and the logged means (``train_stats``) then
+    need neither a torch op nor a synchronisation, and the sequence is one graph."""
 
     def __init__(self, seat, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
-                 betas=(0.9, 0.999), eps=1e-5, max_groups=0):
+                 betas=(0.9, 0.999), eps=1e-5, max_groups=0, clip_range_vf=None, target_kl=None):
         if not isinstance(seat, FusedActorCriticPartner):
             raise TypeError("PPOLearner updates a gym_comm_amd.vec_env.FusedActorCriticPartner")
         pol = seat.policy
@@ -49,6 +55,13 @@ class PPOLearner:
         self.step = z(1, torch.int32)
         self.stats_t = z(len(STATS))
         self.hyper = torch.tensor([lr, clip_range], dtype=torch.float32, device=dev)
+        # the train sequence's device state (include/oc_policy.h: oc_ppo_train); 0 = off
+        self.hyper_ext = torch.tensor([clip_range_vf or 0.0, target_kl or 0.0], dtype=torch.float32, device=dev)
+        # (ctl and acc are views of one buffer: train_stats() fetches both with one copy)
+        self._train_words = z(_lib.PPO_ACC["words"] + _lib.PPO_CTL["words"] // 2, torch.float64)
+        self.acc = self._train_words[:_lib.PPO_ACC["words"]]
+        self.ctl = self._train_words[_lib.PPO_ACC["words"]:].view(torch.int32)
+        self._idx, self._trains = None, {}
         self.grads, o = {}, 0
         for k, t in zip(PARAMS, self._params):
             self.grads[k] = self.grad_flat[o:o + t.numel()].view(t.shape)
@@ -74,6 +87,15 @@ class PPOLearner:
 
     def set_clip_range(self, clip_range):
         self.hyper[1] = float(clip_range)
+
+    def set_clip_range_vf(self, clip_range_vf):
+        """Value clipping of the train sequence (``shuffle="device"``, ``train_graph``); None = off."""
+        self.hyper_ext[0] = float(clip_range_vf or 0.0)
+
+    def set_target_kl(self, target_kl):
+        """The train sequence's early stop: no epoch after one whose mean approx_kl exceeds
+        1.5 ``target_kl``; None = off."""
+        self.hyper_ext[1] = float(target_kl or 0.0)
 
     # ---- one minibatch ----
     def plan(self, B):
@@ -120,10 +142,13 @@ class PPOLearner:
         if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
             raise ValueError("idx: a contiguous int32 [B] tensor on %s" % (self.device,))
         B = idx.numel()
+        self._check_outs(B)
+        _lib.call(self._L, name, self._dev, ctypes.byref(self._cfg(sink, B)), idx.data_ptr(), B)
+
+    def _check_outs(self, B):
         for t in (self.lp_out, self.v_out):
             if t is not None and (t.dtype != torch.float32 or t.numel() < B or not t.is_contiguous()):
                 raise ValueError("lp_out / v_out: contiguous float32 tensors of at least B elements")
-        _lib.call(self._L, name, self._dev, ctypes.byref(self._cfg(sink, B)), idx.data_ptr(), B)
 
     def update(self, sink, idx):
         """One minibatch: loss, gradient, clip, Adam, repack.  Three launches, no synchronisation."""
@@ -150,9 +175,27 @@ class PPOLearner:
         idx = (perm.unsqueeze(1) * g + torch.arange(g, device=self.device)).reshape(-1).to(torch.int32)
         return [b for b in idx.split(int(batch_size)) if b.numel() >= 2]
 
-    def train(self, sink, n_epochs=10, batch_size=None, granule=32, generator=None):
+    def train(self, sink, n_epochs=10, batch_size=None, granule=32, generator=None, shuffle="torch", seed=0):
         """``n_epochs`` passes over a FULL fused sink whose ``compute_returns_and_advantage`` has run
-        (``finish_rollout``).  ``batch_size=None``: the whole buffer as one minibatch."""
+        (``finish_rollout``).  ``batch_size=None``: the whole buffer as one minibatch.
+
+        ``shuffle="torch"``: ``minibatches`` (torch.randperm, ``generator``) and one ``update`` each.
+        ``shuffle="device"``: the train sequence of include/oc_policy.h, launched eagerly -- the
+        permutation of (``seed``, the learner's device-side epoch counter) written into the learner's
+        own index buffer, value clipping (``clip_range_vf``), the KL stop (``target_kl``) and the
+        statistics ``train_stats()`` reports all on the device; the same launches ``train_graph`` captures."""
+        granule = self._check_trainable(sink, granule)
+        if shuffle == "device":
+            return self._sequence(sink, int(n_epochs), batch_size, granule, seed)
+        if shuffle != "torch":
+            raise ValueError("shuffle: 'torch' or 'device' (got %r)" % (shuffle,))
+        T, _, n = sink.obs.shape
+        for _ in range(int(n_epochs)):
+            for idx in self.minibatches(sink, batch_size or T * n, granule, generator):
+                self.update(sink, idx)
+
+    def _check_trainable(self, sink, granule):
+        """train()'s checks of the sink; returns the granule to use (1 if it does not divide the envs)."""
         if not getattr(sink, "fused", False):
             raise ValueError("train() needs a RolloutSink(fused=True): it holds advantages and returns")
         if not getattr(sink, "returns_ready", False):
@@ -160,13 +203,96 @@ class PPOLearner:
                              "(compute_returns_and_advantage) first")
         if not sink.full():
             raise ValueError("train() needs a full sink (%d of %d steps recorded)" % (sink.steps(), sink.n_steps))
-        T, _, n = sink.obs.shape
-        if granule > 1 and n % granule:
-            granule = 1
-        for _ in range(int(n_epochs)):
-            for idx in self.minibatches(sink, batch_size or T * n, granule, generator):
-                self.update(sink, idx)
+        n = sink.obs.shape[2]
+        return 1 if granule > 1 and n % granule else int(granule)
 
     def stats(self):
         """The last minibatch's statistics as a dict: ONE synchronisation, and only when called."""
         return dict(zip(STATS, self.stats_t.cpu().tolist()))
+
+    # ---- the train sequence: a whole train() on device-side state ----
+    def _train_state(self, sink):
+        tr = self._trains.get(id(sink))
+        if tr is None:
+            v = getattr(sink, "values", None)
+            if v is None or v.device != self.device or v.dtype != torch.float32 or not v.is_contiguous() \
+                    or v.shape != sink.advantages.shape:
+                raise ValueError("the sink's values: a contiguous float32 [T][n] tensor on %s" % (self.device,))
+            tr = _lib.PpoTrain(v.data_ptr(), self.hyper_ext.data_ptr(), self.ctl.data_ptr(), self.acc.data_ptr())
+            tr._keep = (v,)
+            self._trains[id(sink)] = tr
+        return tr
+
+    def _sequence(self, sink, n_epochs, batch_size, granule, seed):
+        """train_begin, then per epoch epoch_begin and one train_step per minibatch: a fixed, serial
+        list of launches on the current stream -- no allocation after the first call for a sink's size,
+        no synchronisation.  The minibatches are ``minibatches``' sizes, cut from the index buffer in order."""
+        T, _, n = sink.obs.shape
+        total = T * n
+        bs = int(batch_size or total)
+        if bs < 1:
+            raise ValueError("batch_size must be positive")
+        sizes = [min(bs, total - o) for o in range(0, total, bs)]
+        cuts = [(o, b) for o, b in zip(range(0, total, bs), sizes) if b >= 2]
+        if self._idx is None or self._idx.numel() < total:
+            self._retired.append(self._idx)               # a captured graph may still write to it
+            self._idx = torch.zeros(total, dtype=torch.int32, device=self.device)
+        self._check_outs(max(sizes))
+        idx, tr, L, dev = self._idx.data_ptr(), ctypes.byref(self._train_state(sink)), self._L, self._dev
+        seed = int(seed) & 0xFFFFFFFF
+        _lib.call(L, "oc_policy_ppo_train_begin", dev, tr)
+        for _ in range(n_epochs):
+            _lib.call(L, "oc_policy_ppo_epoch_begin", dev, tr, idx, total, granule, seed)
+            for o, b in cuts:
+                _lib.call(L, "oc_policy_ppo_train_step", dev, ctypes.byref(self._cfg(sink, b)), tr, idx + 4 * o, b)
+
+    def _train_tensors(self):
+        """Everything a train sequence writes that a later one reads."""
+        return list(self._params) + [self.m, self.v, self.step, self._w2t, self.stats_t, self.grad_flat,
+                                     self._train_words] + list(self.seat._w)
+
+    def train_graph(self, sink, n_epochs, batch_size=None, granule=32, seed=0):
+        """``train(shuffle="device")`` captured into ONE graph: a strictly serial stream of launches, no
+        parallel branch.  The sequence runs once eagerly first (every kernel is loaded before the
+        capture), the learner's state is put back, and the capture follows.  Returns an object whose
+        ``replay()`` is one train(): the epoch counter lives on the device, so every replay shuffles anew,
+        and ``set_lr`` / ``set_clip_range`` / ``set_clip_range_vf`` / ``set_target_kl`` act on the next replay."""
+        granule = self._check_trainable(sink, granule)
+        with _lib.on_device(self._dev):
+            state = self._train_tensors()
+            saved = [t.clone() for t in state]
+            self._sequence(sink, 1, batch_size, granule, seed)        # (also sizes the index buffer and the scratch)
+            torch.cuda.synchronize(self.device)
+            with torch.no_grad():
+                for t, s in zip(state, saved):
+                    t.copy_(s)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._sequence(sink, int(n_epochs), batch_size, granule, seed)
+        return TrainGraph(self, sink, graph)
+
+    def train_stats(self):
+        """The reference's logged means over the updates APPLIED in the last train sequence -- policy_loss,
+        value_loss, entropy_loss, approx_kl, clip_fraction, loss -- with ``updates``, ``epochs`` (completed)
+        and ``stopped`` (by the KL rule).  ONE synchronisation, and only when called."""
+        host = self._train_words.cpu()
+        na = _lib.PPO_ACC["words"]
+        acc, ctl = host[:na].tolist(), host[na:].view(torch.int32).tolist()
+        if ctl[_lib.PPO_CTL["error"]]:
+            raise _lib.OcError("the train sequence halted: a permutation walk reached its cap (include/oc_policy.h)")
+        updates = ctl[_lib.PPO_CTL["updates"]]
+        out = {k: (acc[_lib.PPO_ACC["sums"] + i] / updates if updates else float("nan"))
+               for i, k in enumerate(TRAIN_STATS)}
+        out.update(updates=updates, stopped=bool(ctl[_lib.PPO_CTL["stop"]]),
+                   epochs=ctl[_lib.PPO_CTL["epochs"]] + (1 if acc[_lib.PPO_ACC["epoch_count"]] > 0 else 0))
+        return out
+
+
+class TrainGraph:
+    """A captured train sequence (``PPOLearner.train_graph``): ``replay()`` is one train()."""
+
+    def __init__(self, learner, sink, graph):
+        self.learner, self.sink, self.graph = learner, sink, graph
+
+    def replay(self):
+        self.graph.replay()

@@ -134,8 +134,8 @@ OC_API int oc_policy_mlp_ac(const oc_policy_ac_player *players, int32_t num_play
  * What it restates: train() of the reference's PPO (pantheonrl/algos/modular/learn.py:222-334, which
  * is stable-baselines3's), with clip_range_vf = None and use_sde = False as its trainer configures
  * it.  OUT OF SCOPE: the marginal-regularisation term (learn.py:299-318, several partners' logits
- * composed), clip_range_vf, target_kl early stopping (approx_kl is reported for a caller to use),
- * hidden sizes other than 64.
+ * composed), hidden sizes other than 64.  (clip_range_vf and target_kl early stopping: the train
+ * sequence, the last section of this header.)
  *
  * A minibatch is idx, int32 [B], B >= 2: sample i is slot idx[i] / n, env idx[i] % n of tensors
  * shaped as an oc_rollout_buf's (include/oc_rollout.h): obs [T][F][n], timestep double [T][n],
@@ -219,6 +219,110 @@ OC_API int oc_policy_ppo_plan(int32_t F, int32_t C, int32_t B, int32_t max_group
  * F >= 1, F + 2 <= 48, 1 <= C <= 16, B >= 2, obs_type, T n < 2^31, non-NULL pointers. */
 OC_API int oc_policy_ppo_update(const oc_ppo_cfg *cfg, const int32_t *idx, int32_t B, void *stream);
 OC_API int oc_policy_ppo_grad(const oc_ppo_cfg *cfg, const int32_t *idx, int32_t B, void *stream);
+
+/* ---- a whole train() as a fixed sequence of launches on device-side state ----------------------
+ *
+ * What it restates: the loops of the reference's train() around the minibatch (learn.py:222-334) --
+ * the epoch's shuffle, the statistics it logs (means over all minibatches of a train()), its
+ * early stop -- and stable-baselines3's clip_range_vf.  Every decision is taken on the device, so the
+ * sequence
+ *     oc_policy_ppo_train_begin,
+ *     n_epochs x (oc_policy_ppo_epoch_begin, then oc_policy_ppo_train_step per minibatch)
+ * is the same serial list of launches whatever happens in it, never allocates or synchronises, and can
+ * be captured into ONE graph.  A sequence is HALTED when ctl[OC_PPO_CTL_STOP] or
+ * ctl[OC_PPO_CTL_ERROR] is non-zero: every later launch of it returns having written nothing.
+ *
+ * The state, all on the device, the caller's:
+ *   values     float [T][n]  the recorded values (oc_rollout_buf.values), read by value clipping
+ *   hyper_ext  float [2]     clip_range_vf, target_kl; a value <= 0 (or NaN) means off.  Read on the
+ *                            device, like oc_ppo_cfg.hyper: a change needs no new capture
+ *   ctl        int32 [OC_PPO_CTL_WORDS], zero at first:
+ *                [OC_PPO_CTL_STOP]     1 once the KL rule has ended this train
+ *                [OC_PPO_CTL_EPOCH]    permutations drawn since the state was zeroed.  NEVER reset by the
+ *                                      library: each train() sees new permutations
+ *                [OC_PPO_CTL_UPDATES]  minibatch updates applied in this train
+ *                [OC_PPO_CTL_EPOCHS]   epochs of this train CLOSED by a later oc_policy_ppo_epoch_begin; the
+ *                                      epoch still open is complete iff acc[OC_PPO_ACC_EPOCH_COUNT] > 0
+ *                [OC_PPO_CTL_ERROR]    1 if a permutation walk hit its cap (below); sticky, never
+ *                                      cleared by the library; the rest reserved
+ *   acc        double [OC_PPO_ACC_WORDS]:
+ *                [OC_PPO_ACC_EPOCH_KL], [OC_PPO_ACC_EPOCH_COUNT]   the open epoch's sum of the minibatches'
+ *                                      approx_kl, and their number
+ *                [OC_PPO_ACC_SUMS + k], k = 0 .. 5   this train's sums of policy_loss, value_loss,
+ *                                      entropy_loss, approx_kl, clip_fraction, loss
+ *              What is added is the FLOAT statistic oc_policy_ppo_train_step has just written to
+ *              cfg.stats, converted to double, by one thread, in launch order: no atomics, and the same
+ *              sequence gives the same bits.
+ *
+ * The KL rule is the reference's (learn.py:328-332), not stable-baselines3's break in mid-epoch: at
+ * the END of an epoch, if target_kl > 0 and the mean over that epoch's minibatches of approx_kl =
+ * mean(old_lp - lp) exceeds 1.5 target_kl, no further epoch runs.  The comparison is
+ * acc[EPOCH_KL] / acc[EPOCH_COUNT] > 1.5 * (double)target_kl, in double.
+ *
+ * Value clipping, where c = clip_range_vf > 0 (otherwise every output of oc_policy_ppo_train_step is bit
+ * for bit oc_policy_ppo_update's): with old_v the recorded value of the sample, in float32,
+ *     v_pred = old_v + clamp(v - old_v, -c, c)
+ *     value_loss = mean((ret - v_pred)^2)
+ *     d loss / d v = 2 vf_coef (v_pred - ret) / B  where -c <= v - old_v <= c (the ends included, as
+ *                    in torch's clamp backward), 0 elsewhere
+ * and a bad-action sample is excluded as it is from every other term.
+ *
+ * The permutation (gym-comm_amd/csrc/oc_policy_shuffle.h), of 0 .. N - 1, 1 <= N <= 2^30, a function of
+ * (seed, epoch, N) alone, every element on its own; all words uint32, arithmetic modulo 2^32:
+ *     fmix32(h):  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ *     bits  = the smallest even number >= 2 with 2^bits >= N;  half = bits / 2;  mask = 2^half - 1
+ *     key_r = fmix32(seed ^ (0x9E3779B9 * (4 epoch + r + 1))),  r = 0 .. 3
+ *     pass(x):  L = x >> half,  R = x & mask;  for r = 0 .. 3:  (L, R) = (R, L ^ (fmix32(R ^ key_r) & mask));
+ *               the result is (L << half) | R           -- a balanced Feistel network: a bijection of 0 .. 2^bits - 1
+ *     perm[i]:  x = pass(i);  while x >= N:  x = pass(x)        -- cycle walking: a bijection of 0 .. N - 1
+ * The walk is cut after 4096 passes: the element is then -1 and the error word is set.  No bijection
+ * can do that to a walk that starts below N before 2^bits - N + 1 < 3 N + 1 passes, and this one lands below N
+ * with a chance above 1/4 per pass: the cap is there so that a bug cannot hang a GPU. */
+#define OC_PPO_CTL_STOP 0
+#define OC_PPO_CTL_EPOCH 1
+#define OC_PPO_CTL_UPDATES 2
+#define OC_PPO_CTL_EPOCHS 3
+#define OC_PPO_CTL_ERROR 4
+#define OC_PPO_CTL_WORDS 8
+#define OC_PPO_ACC_EPOCH_KL 0
+#define OC_PPO_ACC_EPOCH_COUNT 1
+#define OC_PPO_ACC_SUMS 2
+#define OC_PPO_ACC_WORDS 8
+
+typedef struct {
+  const float *values;      /* float [T][n] */
+  const float *hyper_ext;   /* float [2]: clip_range_vf, target_kl */
+  int32_t *ctl;             /* int32 [OC_PPO_CTL_WORDS] */
+  double *acc;              /* double [OC_PPO_ACC_WORDS] */
+} oc_ppo_train;
+
+/* Host only: out int32 [N] = the permutation above.  Returns non-zero (and says why) for a bad
+ * argument, or if an element came out -1. */
+OC_API int oc_policy_ppo_perm_host(uint32_t seed, int32_t epoch, int32_t N, int32_t *out);
+
+/* One launch of one thread: clears stop, updates, epochs and every sum of acc.  Touches neither the
+ * epoch counter nor the error word. */
+OC_API int oc_policy_ppo_train_begin(const oc_ppo_train *train, void *stream);
+
+/* Two launches; nothing at all is written by either if the sequence is halted when it runs.
+ *   1. one thread closes the epoch before: if this train has an open epoch with minibatches, the KL
+ *      rule (above) is applied to it -- it may set stop, which ends this call's effect here -- and epochs
+ *      is bumped; then the epoch sums are zeroed and the epoch counter is bumped.
+ *   2. the permutation of epoch number (epoch counter - 1), N = count / granule, expanded by the
+ *      granule into idx, int32 [count]:  idx[i * granule + j] = perm[i] * granule + j.
+ * (Two launches: no workgroup reads an epoch number that another one of its launch changes.)
+ * Checked before any device work: non-NULL pointers, granule >= 1 dividing count, count >= 1,
+ * count / granule <= 2^30. */
+OC_API int oc_policy_ppo_epoch_begin(const oc_ppo_train *train, int32_t *idx, int32_t count, int32_t granule,
+                                     uint32_t seed, void *stream);
+
+/* One minibatch of the sequence: oc_policy_ppo_update's three launches and checks (and the train state's
+ * pointers), with value clipping, and with the minibatch's statistics added to the sums and updates
+ * bumped after cfg.stats is written.  Halted: none of the three writes anything -- not the
+ * parameters, m, v, step, the fragments, w2t, grad, scratch, stats (stats[6], [7] included), the sums
+ * or lp_out / v_out. */
+OC_API int oc_policy_ppo_train_step(const oc_ppo_cfg *cfg, const oc_ppo_train *train, const int32_t *idx, int32_t B,
+                                    void *stream);
 
 #ifdef __cplusplus
 }
