@@ -54,6 +54,13 @@ class PolicyAcPlayer(ctypes.Structure):
                 ("comm_row", ctypes.c_void_p), ("log_prob", ctypes.c_void_p), ("value", ctypes.c_void_p)]
 
 
+class PolicyLstmPlayer(ctypes.Structure):
+    """oc_policy_lstm_player (include/oc_policy.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "gates", "head", "head_bias", "h_in", "c_in", "h_out", "c_out", "episode_start", "rng", "given",
+                 "pairs", "move_row", "comm_row", "log_prob", "value", "logits")]
+
+
 class PpoCfg(ctypes.Structure):
     """oc_ppo_cfg (include/oc_policy.h)."""
     _fields_ = [(name, ctypes.c_void_p) for name in
@@ -155,6 +162,12 @@ def _libs_table():
             "oc_policy_ppo_train_begin": (cint, [P(PpoTrain), vp]),
             "oc_policy_ppo_epoch_begin": (cint, [P(PpoTrain), vp, i32, i32, u32, vp]),
             "oc_policy_ppo_train_step": (cint, [P(PpoCfg), P(PpoTrain), vp, i32, vp]),
+            # the recurrent seat: an LSTM actor-critic step
+            "oc_policy_lstm_ksteps": (i32, [i32]),
+            "oc_policy_lstm_pack_gates": (cint, [fp, fp, fp, fp, i32, vp]),
+            "oc_policy_lstm_pack_head": (cint, [fp, fp, i32, vp]),
+            "oc_policy_lstm_pack_head_bias": (cint, [fp, fp, i32, fp]),
+            "oc_policy_lstm_ac": (cint, [P(PolicyLstmPlayer), vp, i32, i32, i32, i64, vp]),
         }),
         "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
             "oc_hostio_abi_version": (cint, None),

@@ -81,10 +81,33 @@ struct PpoLayout {
   }
 };
 
+// ---- the recurrent seat (include/oc_policy.h, last section; oc_policy_lstm.hip) --------------------
+// gates fp16 [4 gates][2][ks][64][8], gates in the order i, f, g, o: element j of lane l, M-tile (gate, m),
+// k-step s of ks = ksteps(F) + LSTM_HSTEPS.  Tile (gate, m) holds rows 64 gate + 32 m .. + 31 of the 256,
+// i.e. units 32 m .. 32 m + 31: the four gates of a unit share a lane and an accumulator register.  The
+// x k-steps come first (k as in w1: < F Wx, F wt, F + 1 b); behind them the four k-steps over h, k
+// permuted to the accumulator order as w2's is (k = -1, hid = the column of Wh).
+constexpr int LSTM_GATES = 4, LSTM_HSTEPS = 4;
+enum { LSTM_I = 0, LSTM_F = 1, LSTM_G = 2, LSTM_O = 3 };
+OC_HD constexpr int lstm_ksteps(int F) { return ksteps(F) + LSTM_HSTEPS; }
+OC_HD constexpr int lstm_gate_elems(int F) { return LSTM_GATES * 2 * lstm_ksteps(F) * 64 * 8; }
+struct GateSrc { int gate, unit, k, hid; };   // row 64 gate + unit of the 256; k >= 0: an x column; else column hid of Wh
+OC_HD constexpr GateSrc lstm_gate_source(int el, int F) {
+  const int ks = lstm_ksteps(F), kx = ksteps(F);
+  const int j = el & 7, l = (el >> 3) & 63, s = (el >> 9) % ks, t = (el >> 9) / ks;
+  const int unit = 32 * (t & 1) + (l & 31);
+  return s < kx ? GateSrc{t >> 1, unit, 16 * s + 8 * (l >> 5) + j, -1}
+                : GateSrc{t >> 1, unit, -1, 16 * (s - kx) + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3)};
+}
+// the head images are w2's and b2's maps (w2_source, b2_row) with other values: log2(e) [W2; wv] and
+// log2(e) [b2; bv], no row-sum fold (the product takes h itself)
+
 // ---- the values: the activation's constants folded in (oc_policy_device.h: sigmoid_complement) ----
 #ifdef __FLT16_MAX__   // (a host compiler without _Float16 still gets the maps above)
 constexpr float FOLD_LOG2E = 1.4426950408889634f;
 constexpr float FOLD_W1 = 2.0f * FOLD_LOG2E, FOLD_W2 = -2.0f * FOLD_LOG2E;
+// the recurrent seat's gates: sigmoid(z) = sigmoid_complement(-log2(e) z), tanh(z) = 1 - 2 sigmoid_complement(2 log2(e) z)
+OC_HD constexpr float lstm_gate_fold(int gate) { return gate == LSTM_G ? FOLD_W1 : -FOLD_LOG2E; }
 
 // the fp16 value a product multiplies by: the product in fp32, rounded once
 OC_HD inline _Float16 fold(float w, float scale) { return (_Float16)(scale * w); }

@@ -1,6 +1,6 @@
 """The players an ``OvercookedVecEnv`` seats (see ``vec_env`` for the overview): ``RandomPartner``,
-``MLPPolicy``, ``MLPActorCritic``, ``TorchPolicyPartner``, ``RecurrentPolicyPartner``, ``FusedMLPPartner``,
-``FusedActorCriticPartner``."""
+``MLPPolicy``, ``MLPActorCritic``, ``LSTMActorCritic``, ``TorchPolicyPartner``, ``RecurrentPolicyPartner``,
+``FusedMLPPartner``, ``FusedActorCriticPartner``, ``FusedRecurrentPartner``."""
 import ctypes
 
 import numpy as np
@@ -123,6 +123,57 @@ class MLPActorCritic(MLPPolicy):
         h = self._hidden(obs)
         out = torch.addmm(self.b2, self.w2, h)                  # [4 + C][n]
         return out[:4], out[4:], torch.addmm(self.bv, self.wv, h).reshape(-1)
+
+
+class LSTMActorCritic(torch.nn.Module):
+    """One LSTM cell of 64 units with the actor's and the critic's heads on its output: the network of
+    include/oc_policy.h's last section in plain float32, gates in ``torch.nn.LSTMCell``'s order i, f, g, o.
+
+        forward(obs, state, episode_start) -> (move logits [4][n], comm logits [C][n], (h, c), value [n])
+
+    The logits are feature-major, as ``MLPPolicy``'s.  ``state`` = (h, c), float32 [n][64] each: env-major,
+    which is what ``RecurrentPolicyPartner``'s protocol asks of a state (``initial_state(n)`` gives one); the
+    fused seat keeps the same numbers transposed, [64][n].  ``episode_start`` float [n] (or None): where it is
+    > 0 the env starts from the zero state, by a select.  ``FusedRecurrentPartner`` runs the same weights as
+    one launch.  Parameters, drawn by ``MLPPolicy``'s rule from one generator in this order: wx [256][F],
+    wt [256][1], b [256][1], wh [256][64], w2 [4 + C][64], b2 [4 + C][1], wv [1][64], bv [1][1]."""
+    feature_major = True
+    hidden = 64
+
+    def __init__(self, num_subtasks, num_comm, seed=0):
+        super().__init__()
+        F, H = 22 + int(num_subtasks) + 2 * int(num_comm), self.hidden
+        g = torch.Generator().manual_seed(int(seed))
+        init = lambda *shape: torch.nn.Parameter(
+            (torch.rand(shape, generator=g) * 2 - 1) / float(np.sqrt(shape[-1])))
+        self.wx, self.wt, self.b, self.wh = init(4 * H, F), init(4 * H, 1), init(4 * H, 1), init(4 * H, H)
+        self.w2, self.b2 = init(4 + int(num_comm), H), init(4 + int(num_comm), 1)
+        self.wv, self.bv = init(1, H), init(1, 1)
+        self.C = int(num_comm)
+
+    def initial_state(self, n, device=None):
+        """(h, c) of n envs that have not started: zeros [n][64]."""
+        dev = device if device is not None else self.wx.device
+        return (torch.zeros((n, self.hidden), dtype=torch.float32, device=dev),
+                torch.zeros((n, self.hidden), dtype=torch.float32, device=dev))
+
+    def forward(self, obs, state, episode_start=None):
+        rows, ts = rows_and_timestep(obs)
+        dt = self.wx.dtype                                          # float32 (float64 after .double(): the tests)
+        if rows.dtype != dt:
+            rows = rows.to(dt)
+        h, c = state[0].T, state[1].T                               # [64][n] views
+        if episode_start is not None:
+            s = (episode_start > 0).unsqueeze(0)
+            h, c = torch.where(s, torch.zeros_like(h), h), torch.where(s, torch.zeros_like(c), c)
+        z = torch.addmm(self.b, self.wx, rows)                      # [256][n]
+        z = torch.addcmul(z, self.wt, ts.to(dt).unsqueeze(0))
+        z = torch.addmm(z, self.wh, h)
+        i, f, g, o = z.view(4, self.hidden, -1)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+        h = torch.sigmoid(o) * torch.tanh(c)
+        out = torch.addmm(self.b2, self.w2, h)                      # [4 + C][n]
+        return out[:4], out[4:], (h.T, c.T), torch.addmm(self.bv, self.wv, h).reshape(-1)
 
 
 class TorchPolicyPartner(_Seat):
@@ -311,6 +362,27 @@ def pack_w2t(L, policy):
     return out
 
 
+def _stream_seed(seed):
+    """The PCG32 stream seed of a fused seat.  None: a different default per seat built (two seats left at
+    their defaults -- an ego and a partner -- must not share per-env random streams: their samples would
+    use the same uniform draw every step); pass a seed for a reproducible stream."""
+    if seed is None:
+        seed = 0x5EED + 1000003 * FusedMLPPartner._seats
+    FusedMLPPartner._seats += 1
+    return int(seed)
+
+
+def _upload(held, arrays, device):
+    """Packed numpy images on the device.  ``held`` None: fresh tensors; otherwise copied into ``held`` in
+    place: a captured graph keeps the addresses."""
+    new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device) for a in arrays)
+    if held is None:
+        return new
+    for old, cur in zip(held, new):
+        old.copy_(cur)
+    return held
+
+
 class _FusedSeat:
     """What the two seats of the hand-written policy kernel share: the checks of the module, the
     default stream seed, the packed weights ``_w`` (three device tensors whose addresses never change:
@@ -320,12 +392,7 @@ class _FusedSeat:
     _value_head = False
 
     def __init__(self, policy, sample, seed, device, keep_logits):
-        # seed=None: a different default per seat built (two seats left at their defaults -- an
-        # ego and a partner -- must not share per-env random streams: their samples would use the
-        # same uniform draw every step); pass a seed for a reproducible stream
-        if seed is None:
-            seed = 0x5EED + 1000003 * FusedMLPPartner._seats
-        FusedMLPPartner._seats += 1
+        seed = _stream_seed(seed)
         if not isinstance(policy, self._module):
             raise TypeError(self._module_error)
         if policy.w1.shape[0] != 64:
@@ -343,13 +410,7 @@ class _FusedSeat:
 
     def refresh(self):
         """(Re)pack the module's current weights into MFMA fragment order and upload them."""
-        new = tuple(torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.device)
-                    for a in pack_fragments(self._L, self.policy, self._value_head))
-        if self._w is None:
-            self._w = new
-        else:                       # in place: a captured graph keeps the addresses
-            for old, cur in zip(self._w, new):
-                old.copy_(cur)
+        self._w = _upload(self._w, pack_fragments(self._L, self.policy, self._value_head), self.device)
 
     def weight_ptrs(self):
         """Device addresses of the three fragment tensors (w1, w2, b2)."""
@@ -554,3 +615,154 @@ class FusedActorCriticPartner(_FusedSeat, _RecordingSeat):
         self.value.copy_(st[3])
         if self.sink is not None:
             self.sink.set_state(st[4])
+
+
+def pack_lstm(L, policy):
+    """An ``LSTMActorCritic``'s current weights as the three images of include/oc_policy.h's last section:
+    numpy ``(gates, head, head_bias)``.  Host code only, as ``pack_fragments``."""
+    F, C = int(policy.wx.shape[1]), int(policy.C)
+    wx, wt, b, wh, w2, b2, wv, bv = (_f32(t) for t in (policy.wx, policy.wt, policy.b, policy.wh, policy.w2,
+                                                       policy.b2, policy.wv, policy.bv))
+    og = np.zeros((4, 2, L.oc_policy_lstm_ksteps(F), 64, 8), np.uint16)
+    oh = np.zeros((4, 64, 8), np.uint16)
+    ob = np.zeros((64, 16), np.float32)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    for rc, what in (
+            (L.oc_policy_lstm_pack_gates(_fp(wx), _fp(wt.reshape(-1)), _fp(b.reshape(-1)), _fp(wh), F, vp(og)),
+             "oc_policy_lstm_pack_gates"),
+            (L.oc_policy_lstm_pack_head(_fp(w2), _fp(wv.reshape(-1)), C, vp(oh)), "oc_policy_lstm_pack_head"),
+            (L.oc_policy_lstm_pack_head_bias(_fp(b2.reshape(-1)), _fp(bv.reshape(-1)), C, _fp(ob)),
+             "oc_policy_lstm_pack_head_bias")):
+        _lib.check(rc, what, L)
+    return og, oh, ob
+
+
+class FusedRecurrentPartner(_RecordingSeat):
+    """An ``LSTMActorCritic`` in the seat of a recurrent player as ONE launch (include/oc_policy.h:
+    ``oc_policy_lstm_ac``): the masked state, the cell (the 256 gate rows on the matrix cores, one wave = 32
+    envs, the update lane-local), both heads, the sampled action written into the env's action rows as
+    they lie, its log-probability and the value -- what ``RecurrentPolicyPartner(LSTMActorCritic(...))`` does
+    in some forty torch launches.  fp16 operands, fp32 accumulation and state: logits within 1.5e-3 and value
+    within 1.4e-3 of the float32 module's, step by step over a 60-step trajectory (measured, not a bound:
+    tests/test_recurrent_seat_gpu.py).
+
+    The seat protocol is ``FusedActorCriticPartner``'s: ``act_into`` (then the sink's ``add``), ``update``,
+    ``reset()``, ``finish_rollout()``, ``refresh()`` after the weights changed, ``get_state`` / ``set_state``.
+    The seat owns ``h``, ``c``, float32 [64][n], updated IN PLACE by the launch (a lane reads exactly the
+    elements it writes); an env whose ``episode_start`` is set starts from the zero state inside the kernel.
+    ``score(obs, state, episode_start, pairs)`` evaluates GIVEN actions from a GIVEN state and writes no
+    state at all: the entry a recurrent update will use."""
+    graph_safe = True
+
+    def __init__(self, policy, sample=True, seed=None, device="cuda", sink=None, keep_logits=False):
+        seed = _stream_seed(seed)
+        if not isinstance(policy, LSTMActorCritic):
+            raise TypeError("FusedRecurrentPartner runs gym_comm_amd.vec_env.LSTMActorCritic; wrap any other module in "
+                            "RecurrentPolicyPartner")
+        if not 1 <= policy.C <= 16:
+            raise ValueError("the fused kernel samples at most 16 comm channels (got %d)" % policy.C)
+        self.policy, self.sample, self.seed = policy, bool(sample), int(seed)
+        self.device = torch.device(device)
+        self.sink = sink
+        self.keep_logits = bool(keep_logits)
+        self._L = _lib.load(lib="policy")
+        self.F, self.C = int(policy.wx.shape[1]), int(policy.C)
+        if self.F + 2 > 64:
+            raise ValueError("the fused kernel takes at most 62 observation rows (got %d)" % self.F)
+        self._rng = self.episode_start = self.log_prob = self.value = self.logits = self.h = self.c = None
+        self._w = None
+        self.refresh()
+
+    def refresh(self):
+        """(Re)pack the module's current weights and upload them, in place after the first time."""
+        self._w = _upload(self._w, pack_lstm(self._L, self.policy), self.device)
+
+    def _buffers(self, n):
+        if self.log_prob is None or self.log_prob.numel() != n:
+            dev = self.device
+            self._rng = pcg32_seed_states(self.seed, (2, n), dev)
+            self.episode_start = torch.ones(n, dtype=torch.float32, device=dev)
+            self.log_prob = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.value = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.h = torch.zeros((64, n), dtype=torch.float32, device=dev)
+            self.c = torch.zeros((64, n), dtype=torch.float32, device=dev)
+            self.logits = torch.zeros((4 + self.C, n), dtype=torch.float32, device=dev) if self.keep_logits else None
+
+    def _launch(self, rows, timestep, state_in, state_out, episode_start, given, move_row, comm_row, log_prob, value):
+        n = rows.shape[1]
+        if rows.shape[0] != self.F:
+            raise ValueError("the policy was built for %d observation rows, the env has %d" % (self.F, rows.shape[0]))
+        if not rows.is_contiguous():
+            raise ValueError("the kernel reads the observation rows as they lie: [F][n], contiguous")
+        for t in tuple(state_in) + tuple(t for t in state_out if t is not None):
+            if t.dtype != torch.float32 or tuple(t.shape) != (64, n) or not t.is_contiguous():
+                raise ValueError("a state tensor is contiguous float32 [64][%d]" % n)
+        if episode_start is not None and (episode_start.dtype != torch.float32 or episode_start.numel() != n
+                                          or not episode_start.is_contiguous()):
+            raise ValueError("episode_start: a contiguous float32 tensor of %d elements" % n)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        use_rng = self.sample and given is None
+        w = self._w
+        pl = _lib.PolicyLstmPlayer(
+            rows.data_ptr(), w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr(), state_in[0].data_ptr(),
+            state_in[1].data_ptr(), ptr(state_out[0]), ptr(state_out[1]), ptr(episode_start),
+            self._rng.data_ptr() if use_rng else None, ptr(given), None, ptr(move_row), ptr(comm_row), ptr(log_prob),
+            ptr(value), ptr(self.logits) if given is None else None)
+        _lib.call(self._L, "oc_policy_lstm_ac", rows.device.index, ctypes.byref(pl), timestep.data_ptr(),
+                  self.F, self.C, OBS_TYPE[rows.dtype], n)
+
+    def act_into(self, obs, move_row, comm_row):
+        """ONE launch: the actions into ``move_row`` / ``comm_row`` (the env's own rows, no copy),
+        ``self.log_prob``, ``self.value`` and the new ``self.h`` / ``self.c``; then the sink's ``add``."""
+        rows, ts = rows_and_timestep(obs)
+        n = rows.shape[1]
+        self._buffers(n)
+        row = FusedActorCriticPartner._action_row
+        state = (self.h, self.c)
+        self._launch(rows, ts, state, state, self.episode_start, None, row(move_row, n), row(comm_row, n),
+                     self.log_prob, self.value)
+        if self.sink is not None:
+            self.sink.add(rows, ts, move_row, comm_row, self.log_prob, self.value, self.episode_start)
+
+    def score(self, obs, state, episode_start, pairs):
+        """(log_prob [n], value [n]) of GIVEN actions, int32 [n][2] (move, comm), from the GIVEN ``state`` =
+        (h, c), float32 [64][n], and ``episode_start`` (float32 [n], or None) under the current weights: one
+        launch, fresh tensors.  n is the scored batch's own; neither ``state`` nor anything of the seat --
+        its own state, streams, ``episode_start``, ``log_prob``, ``value``, kept logits -- is written.  An
+        index outside its head's range yields -inf."""
+        rows, ts = rows_and_timestep(obs)
+        n = rows.shape[1]
+        if pairs.dtype != torch.int32 or tuple(pairs.shape) != (n, 2) or not pairs.is_contiguous():
+            raise ValueError("pairs: a contiguous int32 [%d][2] tensor" % n)
+        lp = torch.empty(n, dtype=torch.float32, device=rows.device)
+        val = torch.empty(n, dtype=torch.float32, device=rows.device)
+        self._launch(rows, ts, tuple(state), (None, None), episode_start, pairs, None, None, lp, val)
+        return lp, val
+
+    def reset(self):
+        """A fresh rollout: every env starts an episode (called by ``reset_tensors``); the kernel's select
+        then takes the zero state whatever ``h`` / ``c`` hold."""
+        if self.episode_start is not None:
+            self.episode_start.fill_(1.0)
+
+    def update(self, rewards, dones):
+        """pantheonrl's ``Agent.update(reward, done)`` for the batch, on buffers that exist by now."""
+        self._buffers(dones.numel())
+        super().update(rewards, dones)
+
+    def get_state(self, n):
+        """The seat's mutable state: its random streams, ``episode_start``, the last ``log_prob`` / ``value``,
+        the sink's position, ``h`` and ``c``."""
+        self._buffers(n)
+        return (self._rng.clone(), self.episode_start.clone(), self.log_prob.clone(), self.value.clone(),
+                None if self.sink is None else self.sink.get_state(), self.h.clone(), self.c.clone())
+
+    def set_state(self, st):
+        self._rng.copy_(st[0])
+        self.episode_start.copy_(st[1])
+        self.log_prob.copy_(st[2])
+        self.value.copy_(st[3])
+        if self.sink is not None:
+            self.sink.set_state(st[4])
+        self.h.copy_(st[5])
+        self.c.copy_(st[6])

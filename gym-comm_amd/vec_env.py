@@ -61,8 +61,9 @@ import torch
 from .batched import BatchedOvercooked
 from .hostio import MappedBuffer, SPACE_DTYPE, TRANSPORTS  # noqa: F401 (re-exported)
 from .envs import OvercookedEnvironment, _arg, make_spaces
-from .partners import (FusedActorCriticPartner, FusedMLPPartner, MLPActorCritic, MLPPolicy,  # noqa: F401 (re-exported)
-                       RandomPartner, RecurrentPolicyPartner, TorchPolicyPartner)
+from .partners import (FusedActorCriticPartner, FusedMLPPartner, FusedRecurrentPartner,  # noqa: F401 (re-exported)
+                       LSTMActorCritic, MLPActorCritic, MLPPolicy, RandomPartner, RecurrentPolicyPartner,
+                       TorchPolicyPartner)
 from .rollout import RolloutSink  # noqa: F401 (re-exported)
 from .learner import PPOLearner  # noqa: F401 (re-exported)
 

@@ -324,6 +324,95 @@ OC_API int oc_policy_ppo_epoch_begin(const oc_ppo_train *train, int32_t *idx, in
 OC_API int oc_policy_ppo_train_step(const oc_ppo_cfg *cfg, const oc_ppo_train *train, const int32_t *idx, int32_t B,
                                     void *stream);
 
+/* ---- the recurrent seat: an LSTM actor-critic step in one launch ---------------------------------
+ *
+ * What it stands in for: the forward of the RECURRENT learner the reference seats on both sides of the
+ * env (trainer.py:92-112: RecurrentPPO('MultiInputPolicy', ...), for the partner inside OnPolicyAgent) --
+ * one LSTM cell of 64 units shared by actor and critic, its state kept per env and put back to zero
+ * where an episode starts.  OUT OF SCOPE: the update (backpropagation through time), hidden sizes other
+ * than 64, a separate critic LSTM.
+ *
+ * The network (gym-comm_amd/partners.py: LSTMActorCritic), per env, H = 64, F observation rows x, gates
+ * in torch.nn.LSTMCell's order i, f, g, o:
+ *     s      = episode_start > 0                                  (float [n]; NULL = no env starts)
+ *     h_in   = s ? 0 : h_prev;   c_in = s ? 0 : c_prev            a SELECT, not a product: a NaN or an
+ *                                                                 infinity in a starting env's old state
+ *                                                                 does not survive
+ *     z      = Wx x + wt * timestep + b + Wh h_in                 256 = 4 x 64 rows, row 64 gate + unit
+ *     i, f, o = sigmoid(z_i), sigmoid(z_f), sigmoid(z_o);   g = tanh(z_g)
+ *     c      = f * c_in + i * g;   h = o * tanh(c)
+ *     logits = W2 h + b2   (4 move, C <= 16 comm);   value = wv . h + bv
+ * and the action, its log-probability and the value leave through oc_policy_mlp_ac's tail as it is: the
+ * same sampler, streams, `given` mode and -inf rule, the value in row 8 of the head product.
+ *
+ * Roundings (everything not named here is float32; r(a) = 1 / (2^a + 1) by v_exp_f32, an add, v_rcp_f32):
+ *   - features, timestep and the constant 1 go to fp16 as in oc_policy_mlp; h_in is the stored float32
+ *     value (after the select) rounded to fp16
+ *   - the gate weights are folded and rounded to fp16: -log2(e) [Wx | wt | b | Wh] for i, f, o, so that
+ *     sigmoid(z) = r(a) of the product a; 2 log2(e) [...] for g, so that tanh(z) = 1 - 2 r(a).  One product
+ *     per row, accumulated in float32 from 0: the x k-steps first, then the four over h
+ *   - c = (f * c_in) + (i * g): two products and their sum, each rounded (no contraction); it is stored
+ *     unrounded.  tanh(c) = 1 - 2 r((2 log2(e)) * c), with the float 2 log2(e) = 2.885390043258667f
+ *   - h = o * tanh(c) is stored as float32, unrounded; the head product takes fp16(h) against log2(e) [W2; wv]
+ *     in fp16, starts from log2(e) [b2; bv] in float32 (the float32 product, no row-sum fold) and delivers
+ *     the logits and the value in base 2, which the tail converts (out * ln 2)
+ * Against the plain float32 module the logits stay within 1.5e-3 and the value within 1.4e-3: the largest
+ * difference MEASURED over a 60-step trajectory of 64 envs with the weights at 4 x the init scale, each step
+ * taken from the kernel's own previous state (tests/test_recurrent_seat_gpu.py; a figure, not a bound).
+ *
+ * One wave = 32 envs (v_mfma_f32_32x32x16_f16).  The 256 gate rows are 8 M-tiles; tile (gate, m) holds
+ * units 32 m .. 32 m + 31, so the four gates of a unit arrive in the same lane and the same accumulator
+ * register and the cell update is lane-local; h leaves the accumulators already in the B-operand order of
+ * the head product and of the next step's recurrent product.
+ *   gates      fp16 [4][2][ks][64 lanes][8], ks = oc_policy_lstm_ksteps(F) = oc_policy_ksteps(F) + 4:
+ *              element j of lane l, tile (gate, m), k-step s.  For s < oc_policy_ksteps(F) the folded
+ *              [Wx | wt | b | 0...][64 gate + 32 m + (l & 31)][16 s + 8 (l >> 5) + j]; for the four k-steps
+ *              over h, s' = s - oc_policy_ksteps(F): the folded Wh[64 gate + 32 m + (l & 31)][16 s' +
+ *              8 (j >> 2) + 4 (l >> 5) + (j & 3)] (k permuted to the accumulator order, as w2's)
+ *   head       fp16 [4][64 lanes][8]: oc_policy_pack_w2v's layout (the value head in row 8) holding
+ *              log2(e) [W2; wv]
+ *   head_bias  fp32 [64 lanes][16]: oc_policy_pack_b2v's layout holding log2(e) [b2; bv]
+ * State: h, c float [64][n], unit-major with the envs contiguous, like the observation rows.  Lane l of
+ * a wave reads exactly the units it writes, of its own env -- those whose accumulator row has its
+ * 4 (l >> 5) half: unit 32 m + (q & 3) + 8 (q >> 2) + 4 (l >> 5) for register q of tile m -- and reads all of
+ * them before it writes any, so h_out / c_out MAY ALIAS h_in / c_in (a seat updates its state in place).
+ * No other overlap between the tensors of a call is allowed. */
+typedef struct {
+  const void *obs;            /* the player's observation rows: [F][n], element type `obs_type` */
+  const uint16_t *gates;      /* the three images (above) */
+  const uint16_t *head;
+  const float *head_bias;
+  const float *h_in, *c_in;   /* float [64][n] */
+  float *h_out, *c_out;       /* float [64][n]; NULL = not written; may alias h_in / c_in */
+  const float *episode_start; /* optional float [n]: > 0 = this env starts from the zero state */
+  uint32_t *rng;              /* the rest with oc_policy_ac_player's meanings: uint32 [2][n] or NULL (greedy) */
+  const int32_t *given;       /* optional int32 [n][2]: score THESE actions; rng is then left alone */
+  int32_t *pairs;             /* optional out, int32 [n][2] */
+  int32_t *move_row;          /* optional out, int32 [n] */
+  int32_t *comm_row;          /* optional out, int32 [n]; given together with move_row */
+  float *log_prob;            /* optional out, float [n] */
+  float *value;               /* optional out, float [n] */
+  float *logits;              /* optional out (tests), float [4 + C][n], natural log */
+} oc_policy_lstm_player;
+
+/* k-steps of the gate product for F observation rows: oc_policy_ksteps(F) over x, then 4 over h */
+OC_API int32_t oc_policy_lstm_ksteps(int32_t F);
+
+/* Host-side packing (plain row-major fp32 in, fragment order out).
+ *   wx [256][F], wt [256], b [256], wh [256][64]  ->  out fp16 [4][2][ks][64][8]
+ *   w2 [4 + C][64], wv [64]                       ->  out fp16 [4][64][8]
+ *   b2 [4 + C], bv [1]                            ->  out fp32 [64][16] */
+OC_API int oc_policy_lstm_pack_gates(const float *wx, const float *wt, const float *b, const float *wh, int32_t F,
+                                     uint16_t *out);
+OC_API int oc_policy_lstm_pack_head(const float *w2, const float *wv, int32_t C, uint16_t *out);
+OC_API int oc_policy_lstm_pack_head_bias(const float *b2, const float *bv, int32_t C, float *out);
+
+/* One launch for n envs; timestep, F, C, obs_type as for oc_policy_mlp.  Checked before any device work:
+ * F >= 1, F + 2 <= 64, 1 <= C <= 16, obs_type, n >= 0, 64 n < 2^31, non-NULL timestep, obs, images and
+ * h_in / c_in, move_row and comm_row together.  Never allocates or synchronises; capturable. */
+OC_API int oc_policy_lstm_ac(const oc_policy_lstm_player *pl, const double *timestep, int32_t F, int32_t C,
+                             int32_t obs_type, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
