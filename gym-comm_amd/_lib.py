@@ -74,6 +74,19 @@ class PpoCfg(ctypes.Structure):
                [("max_groups", ctypes.c_int32), ("lp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
 
 
+class RppoCfg(ctypes.Structure):
+    """oc_rppo_cfg (include/oc_policy.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "timestep", "actions", "log_probs", "advantages", "returns", "episode_starts", "h0", "c0")] + \
+               [("n", ctypes.c_int64), ("T", ctypes.c_int32), ("F", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("obs_type", ctypes.c_int32)] + \
+               [(name, ctypes.c_void_p) for name in
+                ("gates", "head", "head_bias", "bwd", "p_wx", "p_wt", "p_b", "p_wh", "p_w2", "p_b2", "p_wv", "p_bv",
+                 "m", "v", "step", "grad", "scratch", "stats", "hyper")] + \
+               [(name, ctypes.c_float) for name in ("ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps")] + \
+               [("max_groups", ctypes.c_int32), ("lp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
+
+
 class PpoTrain(ctypes.Structure):
     """oc_ppo_train (include/oc_policy.h): the train sequence's device state."""
     _fields_ = [(name, ctypes.c_void_p) for name in ("values", "hyper_ext", "ctl", "acc")]
@@ -168,6 +181,12 @@ def _libs_table():
             "oc_policy_lstm_pack_head": (cint, [fp, fp, i32, vp]),
             "oc_policy_lstm_pack_head_bias": (cint, [fp, fp, i32, fp]),
             "oc_policy_lstm_ac": (cint, [P(PolicyLstmPlayer), vp, i32, i32, i32, i64, vp]),
+            # the recurrent seat's PPO update
+            "oc_policy_rppo_plan": (cint, [i32, i32, i32, i32, i32, P(i64)]),
+            "oc_policy_rppo_pack_bwd_elems": (i32, None),
+            "oc_policy_rppo_pack_bwd": (cint, [fp, fp, fp, i32, fp]),
+            "oc_policy_rppo_update": (cint, [P(RppoCfg), vp, i32, vp]),
+            "oc_policy_rppo_grad": (cint, [P(RppoCfg), vp, i32, vp]),
         }),
         "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
             "oc_hostio_abi_version": (cint, None),

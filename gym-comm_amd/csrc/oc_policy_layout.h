@@ -81,7 +81,7 @@ struct PpoLayout {
   }
 };
 
-// ---- the recurrent seat (include/oc_policy.h, last section; oc_policy_lstm.hip) --------------------
+// ---- the recurrent seat (include/oc_policy.h, its own section; oc_policy_lstm.hip) -----------------
 // gates fp16 [4 gates][2][ks][64][8], gates in the order i, f, g, o: element j of lane l, M-tile (gate, m),
 // k-step s of ks = ksteps(F) + LSTM_HSTEPS.  Tile (gate, m) holds rows 64 gate + 32 m .. + 31 of the 256,
 // i.e. units 32 m .. 32 m + 31: the four gates of a unit share a lane and an accumulator register.  The
@@ -102,12 +102,49 @@ OC_HD constexpr GateSrc lstm_gate_source(int el, int F) {
 // the head images are w2's and b2's maps (w2_source, b2_row) with other values: log2(e) [W2; wv] and
 // log2(e) [b2; bv], no row-sum fold (the product takes h itself)
 
+// ---- the recurrent update (include/oc_policy.h, last section; oc_policy_rppo.hip) -------------------
+// offsets of the eight tensors in the flat parameter vector [P], and where a product's logical
+// coordinates land in it (-1: none): row = 64 gate + unit of the 256 gate rows
+struct RppoLayout {
+  int F, C, wt, b, wh, w2, b2, wv, bv, P;
+  OC_HD constexpr RppoLayout(int F_, int C_)
+      : F(F_), C(C_), wt(256 * F_), b(wt + 256), wh(b + 256), w2(wh + 256 * HIDDEN), b2(w2 + (4 + C_) * 64),
+        wv(b2 + 4 + C_), bv(wv + 64), P(bv + 1) {}
+  OC_HD constexpr int gate(int row, int k) const {
+    return k < 0 ? -1 : k < F ? row * F + k : k == F ? wt + row : k == F + 1 ? b + row : -1;
+  }
+  OC_HD constexpr int rec(int row, int hid) const { return wh + row * HIDDEN + hid; }
+  OC_HD constexpr int second(int row, int hid) const {
+    const int lg = logit_of_row(row, C);
+    return lg >= 0 ? w2 + lg * 64 + hid : row == VALUE_ROW ? wv + hid : -1;
+  }
+  OC_HD constexpr int bias(int row) const {
+    const int lg = logit_of_row(row, C);
+    return lg >= 0 ? b2 + lg : row == VALUE_ROW ? bv : -1;
+  }
+};
+// the backward's image, fp32 [LSTM_BWD_ELEMS]: first wht [2][8][16][64] -- lane l of k-step (tile, q), M-tile
+// m: Wh transposed, k in the order in which d z sits in the gate product's accumulators (register q of tile
+// (gate, mm) = row 64 gate + 32 mm + acc_row(q, l >> 5)), hidden unit 32 m + (l & 31) -- then the head's
+// w2t [2][16][64] through w2t_source.  The values are those of the network the fp16 images represent: the
+// folded fp16 weight times the inverse of its fold (lstm_gate_unfold; ln 2 for the head).
+constexpr int LSTM_WHT_ELEMS = 2 * 8 * 16 * 64;
+constexpr int LSTM_BWD_ELEMS = LSTM_WHT_ELEMS + W2T_ELEMS;
+struct GateHid { int gate, unit, hid; };   // row 64 gate + unit of Wh, column hid
+OC_HD constexpr GateHid lstm_wht_source(int el) {
+  const int l = el & 63, q = (el >> 6) & 15, t = (el >> 10) & 7, m = el >> 13;
+  return {t >> 1, 32 * (t & 1) + acc_row(q, l >> 5), 32 * m + (l & 31)};
+}
+
 // ---- the values: the activation's constants folded in (oc_policy_device.h: sigmoid_complement) ----
 #ifdef __FLT16_MAX__   // (a host compiler without _Float16 still gets the maps above)
 constexpr float FOLD_LOG2E = 1.4426950408889634f;
 constexpr float FOLD_W1 = 2.0f * FOLD_LOG2E, FOLD_W2 = -2.0f * FOLD_LOG2E;
 // the recurrent seat's gates: sigmoid(z) = sigmoid_complement(-log2(e) z), tanh(z) = 1 - 2 sigmoid_complement(2 log2(e) z)
 OC_HD constexpr float lstm_gate_fold(int gate) { return gate == LSTM_G ? FOLD_W1 : -FOLD_LOG2E; }
+// the inverse folds, as the recurrent update's backward image multiplies by them (one fp32 product)
+constexpr float FOLD_LN2 = 0.6931471805599453f;
+OC_HD constexpr float lstm_gate_unfold(int gate) { return gate == LSTM_G ? 0.5f * FOLD_LN2 : -FOLD_LN2; }
 
 // the fp16 value a product multiplies by: the product in fp32, rounded once
 OC_HD inline _Float16 fold(float w, float scale) { return (_Float16)(scale * w); }

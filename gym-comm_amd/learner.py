@@ -1,20 +1,111 @@
 """``PPOLearner``: the PPO update of a ``FusedActorCriticPartner``'s ``MLPActorCritic`` as three
-launches per minibatch (include/oc_policy.h: ``oc_policy_ppo_update``) -- see ``vec_env`` for the overview."""
+launches per minibatch (include/oc_policy.h: ``oc_policy_ppo_update``); ``RecurrentPPOLearner``: the update of a
+``FusedRecurrentPartner``'s ``LSTMActorCritic`` over whole recorded sequences, six launches per minibatch
+(``oc_policy_rppo_update``) -- see ``vec_env`` for the overview."""
 import ctypes
 
 import torch
 
 from . import _lib
 from .batched import OBS_TYPE
-from .partners import FusedActorCriticPartner, pack_w2t
+from .partners import FusedActorCriticPartner, FusedRecurrentPartner, pack_lstm_bwd, pack_w2t
 
 STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "grad_norm",
          "adv_mean", "adv_std", "bad", "loss")
 PARAMS = ("w1", "wt", "b1", "w2", "b2", "wv", "bv")        # the order of the flat gradient [P]
 TRAIN_STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "loss")   # train_stats()
+RECURRENT_PARAMS = ("wx", "wt", "b", "wh", "w2", "b2", "wv", "bv")   # the order of the recurrent learner's [P]
 
 
-class PPOLearner:
+class _Learner:
+    """What the two learners share: the checked master weights, Adam's state, the flat gradient with its views,
+    the statistics, the device-side hyper-parameters, the scratch that regrows by retiring, and the checks of
+    a sink before ``train()``."""
+
+    def _init_state(self, seat, names, P, lr, clip_range, ent_coef, vf_coef, max_grad_norm, betas, eps, max_groups):
+        pol = seat.policy
+        self.seat, self.policy = seat, pol
+        self._L = seat._L
+        self.F, self.C = seat.F, seat.C
+        self._params = [getattr(pol, k) for k in names]
+        for k, t in zip(names, self._params):
+            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("parameter %s: a contiguous float32 CUDA tensor (there is no CPU fallback)" % k)
+            if t.device != seat.weight_device:
+                raise ValueError("parameter %s lives on %s, the seat's packed weights on %s" % (k, t.device, seat.weight_device))
+        dev = self.device = self._params[0].device
+        self._dev = dev.index if dev.index is not None else torch.cuda.current_device()
+        self.P = int(P)
+        if self.P != sum(t.numel() for t in self._params):
+            raise ValueError("the module has %d parameters, the kernel's layout %d" % (sum(t.numel() for t in self._params), P))
+        z = self._zeros
+        self.m, self.v, self.grad_flat = z(self.P), z(self.P), z(self.P)
+        self.step = z(1, torch.int32)
+        self.stats_t = z(len(STATS))
+        self.hyper = torch.tensor([lr, clip_range], dtype=torch.float32, device=dev)
+        self.grads, o = {}, 0
+        for k, t in zip(names, self._params):
+            self.grads[k] = self.grad_flat[o:o + t.numel()].view(t.shape)
+            o += t.numel()
+        self.ent_coef, self.vf_coef, self.max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
+        self.betas, self.eps, self.max_groups = (float(betas[0]), float(betas[1])), float(eps), int(max_groups)
+        self._scratch, self._retired = None, []
+        self._cfgs = {}
+        self.lp_out = self.v_out = None          # set to float tensors to receive the forward (tests)
+
+    def _zeros(self, n, dt=torch.float32):
+        return torch.zeros(n, dtype=dt, device=self.device)
+
+    def _grow_scratch(self, need):
+        if self._scratch is None or self._scratch.numel() < need:
+            self._retired.append(self._scratch)           # a captured graph may still write to it
+            self._scratch = torch.zeros(need, dtype=torch.float32, device=self.device)
+            self._cfgs.clear()
+
+    def _sink_tensors(self, sink, names):
+        """The sink's tensors a cfg points at, checked; returns (tensors, T, n)."""
+        for name in names:
+            t = getattr(sink, name, None)
+            if t is None or t.device != self.device or not t.is_contiguous():
+                raise ValueError("the sink's %s: a contiguous tensor on %s (a fused sink has advantages / returns)"
+                                 % (name, self.device))
+        T, F, n = sink.obs.shape
+        if F != self.F:
+            raise ValueError("the policy was built for %d observation rows, the sink holds %d" % (self.F, F))
+        if sink.obs.dtype not in OBS_TYPE:
+            raise ValueError("the kernel reads int32, int8 or float32 rows (got %s)" % (sink.obs.dtype,))
+        return tuple(getattr(sink, name) for name in names), T, n
+
+    # ---- hyper-parameters read on the device ----
+    def set_lr(self, lr):
+        self.hyper[0] = float(lr)
+
+    def set_clip_range(self, clip_range):
+        self.hyper[1] = float(clip_range)
+
+    def _check_outs(self, B):
+        for t in (self.lp_out, self.v_out):
+            if t is not None and (t.dtype != torch.float32 or t.numel() < B or not t.is_contiguous()):
+                raise ValueError("lp_out / v_out: contiguous float32 tensors of at least B elements")
+
+    def _check_trainable(self, sink, granule):
+        """train()'s checks of the sink; returns the granule to use (1 if it does not divide the envs)."""
+        if not getattr(sink, "fused", False):
+            raise ValueError("train() needs a RolloutSink(fused=True): it holds advantages and returns")
+        if not getattr(sink, "returns_ready", False):
+            raise ValueError("train() needs the sink's advantages: call finish_rollout() "
+                             "(compute_returns_and_advantage) first")
+        if not sink.full():
+            raise ValueError("train() needs a full sink (%d of %d steps recorded)" % (sink.steps(), sink.n_steps))
+        n = sink.obs.shape[2]
+        return 1 if granule > 1 and n % granule else int(granule)
+
+    def stats(self):
+        """The last minibatch's statistics as a dict: ONE synchronisation, and only when called."""
+        return dict(zip(STATS, self.stats_t.cpu().tolist()))
+
+
+class PPOLearner(_Learner):
     """What ``train()`` of the reference's PPO does per minibatch (pantheonrl/algos/modular/learn.py:
     222-334, stable-baselines3's, ``clip_range_vf=None``, no marginal regularisation) for the module
     of a ``FusedActorCriticPartner``: advantage normalisation, the clipped loss, its gradient, the
@@ -33,28 +124,10 @@ class PPOLearner:
                  betas=(0.9, 0.999), eps=1e-5, max_groups=0, clip_range_vf=None, target_kl=None):
         if not isinstance(seat, FusedActorCriticPartner):
             raise TypeError("PPOLearner updates a gym_comm_amd.vec_env.FusedActorCriticPartner")
-        pol = seat.policy
-        self.seat, self.policy = seat, pol
-        self._L = seat._L
-        self.F, self.C = seat.F, seat.C
-        self._params = [getattr(pol, k) for k in PARAMS]
-        for k, t in zip(PARAMS, self._params):
-            if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("parameter %s: a contiguous float32 CUDA tensor (there is no CPU fallback)" % k)
-            if t.device != seat.weight_device:
-                raise ValueError("parameter %s lives on %s, the seat's packed weights on %s" % (k, t.device, seat.weight_device))
-        dev = self.device = self._params[0].device
-        self._dev = dev.index if dev.index is not None else torch.cuda.current_device()
         plan = (ctypes.c_int32 * 4)()
-        _lib.check(self._L.oc_policy_ppo_plan(self.F, self.C, 2, 0, plan), "oc_policy_ppo_plan", self._L)
-        P = self.P = int(plan[2])
-        if P != sum(t.numel() for t in self._params):
-            raise ValueError("the module has %d parameters, the kernel's layout %d" % (sum(t.numel() for t in self._params), P))
-        z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
-        self.m, self.v, self.grad_flat = z(P), z(P), z(P)
-        self.step = z(1, torch.int32)
-        self.stats_t = z(len(STATS))
-        self.hyper = torch.tensor([lr, clip_range], dtype=torch.float32, device=dev)
+        _lib.check(seat._L.oc_policy_ppo_plan(seat.F, seat.C, 2, 0, plan), "oc_policy_ppo_plan", seat._L)
+        self._init_state(seat, PARAMS, plan[2], lr, clip_range, ent_coef, vf_coef, max_grad_norm, betas, eps, max_groups)
+        z, dev = self._zeros, self.device
         # the train sequence's device state (include/oc_policy.h: oc_ppo_train); 0 = off
         self.hyper_ext = torch.tensor([clip_range_vf or 0.0, target_kl or 0.0], dtype=torch.float32, device=dev)
         # (ctl and acc are views of one buffer: train_stats() fetches both with one copy)
@@ -62,16 +135,7 @@ class PPOLearner:
         self.acc = self._train_words[:_lib.PPO_ACC["words"]]
         self.ctl = self._train_words[_lib.PPO_ACC["words"]:].view(torch.int32)
         self._idx, self._trains = None, {}
-        self.grads, o = {}, 0
-        for k, t in zip(PARAMS, self._params):
-            self.grads[k] = self.grad_flat[o:o + t.numel()].view(t.shape)
-            o += t.numel()
-        self.ent_coef, self.vf_coef, self.max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
-        self.betas, self.eps, self.max_groups = (float(betas[0]), float(betas[1])), float(eps), int(max_groups)
-        self._scratch, self._retired = None, []
         self._w2t = z(2 * 16 * 64)
-        self._cfgs = {}
-        self.lp_out = self.v_out = None          # set to float [B] tensors to receive the forward (tests)
         self.refresh()
 
     def refresh(self):
@@ -80,13 +144,6 @@ class PPOLearner:
         graph keeps the address).  ``update`` keeps both current itself."""
         self.seat.refresh()
         self._w2t.copy_(torch.from_numpy(pack_w2t(self._L, self.policy).reshape(-1)))
-
-    # ---- hyper-parameters read on the device ----
-    def set_lr(self, lr):
-        self.hyper[0] = float(lr)
-
-    def set_clip_range(self, clip_range):
-        self.hyper[1] = float(clip_range)
 
     def set_clip_range_vf(self, clip_range_vf):
         """Value clipping of the train sequence (``shuffle="device"``, ``train_graph``); None = off."""
@@ -105,36 +162,22 @@ class PPOLearner:
         return tuple(int(v) for v in plan)
 
     def _cfg(self, sink, B):
-        need = max(self.plan(B)[3], 64 * (self.P + 8))    # the default cap's worth at once: no regrowth
-        if self._scratch is None or self._scratch.numel() < need:
-            self._retired.append(self._scratch)           # a captured graph may still write to it
-            self._scratch = torch.zeros(need, dtype=torch.float32, device=self.device)
-            self._cfgs.clear()
+        self._grow_scratch(max(self.plan(B)[3], 64 * (self.P + 8)))    # the default cap's worth at once: no regrowth
         key = (id(sink), self.max_groups, None if self.lp_out is None else self.lp_out.data_ptr(),
                None if self.v_out is None else self.v_out.data_ptr())
         cfg = self._cfgs.get(key)
         if cfg is None:
-            for name in ("obs", "timestep", "actions", "log_probs", "advantages", "returns"):
-                t = getattr(sink, name, None)
-                if t is None or t.device != self.device or not t.is_contiguous():
-                    raise ValueError("the sink's %s: a contiguous tensor on %s (a fused sink has advantages / returns)"
-                                     % (name, self.device))
-            T, F, n = sink.obs.shape
-            if F != self.F:
-                raise ValueError("the policy was built for %d observation rows, the sink holds %d" % (self.F, F))
-            if sink.obs.dtype not in OBS_TYPE:
-                raise ValueError("the kernel reads int32, int8 or float32 rows (got %s)" % (sink.obs.dtype,))
+            keep, T, n = self._sink_tensors(sink, ("obs", "timestep", "actions", "log_probs", "advantages", "returns"))
             ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
             cfg = _lib.PpoCfg(
-                sink.obs.data_ptr(), sink.timestep.data_ptr(), sink.actions.data_ptr(), sink.log_probs.data_ptr(),
-                sink.advantages.data_ptr(), sink.returns.data_ptr(), n, T, F, self.C, OBS_TYPE[sink.obs.dtype],
+                *[t.data_ptr() for t in keep], n, T, self.F, self.C, OBS_TYPE[sink.obs.dtype],
                 *self.seat.weight_ptrs(), self._w2t.data_ptr(),
                 *[t.data_ptr() for t in self._params],
                 self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.grad_flat.data_ptr(),
                 self._scratch.data_ptr(), self.stats_t.data_ptr(), self.hyper.data_ptr(),
                 self.ent_coef, self.vf_coef, self.max_grad_norm, self.betas[0], self.betas[1], self.eps,
                 self.max_groups, ptr(self.lp_out), ptr(self.v_out))
-            cfg._keep = (sink.obs, sink.timestep, sink.actions, sink.log_probs, sink.advantages, sink.returns)
+            cfg._keep = keep
             self._cfgs[key] = cfg
         return cfg
 
@@ -144,11 +187,6 @@ class PPOLearner:
         B = idx.numel()
         self._check_outs(B)
         _lib.call(self._L, name, self._dev, ctypes.byref(self._cfg(sink, B)), idx.data_ptr(), B)
-
-    def _check_outs(self, B):
-        for t in (self.lp_out, self.v_out):
-            if t is not None and (t.dtype != torch.float32 or t.numel() < B or not t.is_contiguous()):
-                raise ValueError("lp_out / v_out: contiguous float32 tensors of at least B elements")
 
     def update(self, sink, idx):
         """One minibatch: loss, gradient, clip, Adam, repack.  Three launches, no synchronisation."""
@@ -193,22 +231,6 @@ class PPOLearner:
         for _ in range(int(n_epochs)):
             for idx in self.minibatches(sink, batch_size or T * n, granule, generator):
                 self.update(sink, idx)
-
-    def _check_trainable(self, sink, granule):
-        """train()'s checks of the sink; returns the granule to use (1 if it does not divide the envs)."""
-        if not getattr(sink, "fused", False):
-            raise ValueError("train() needs a RolloutSink(fused=True): it holds advantages and returns")
-        if not getattr(sink, "returns_ready", False):
-            raise ValueError("train() needs the sink's advantages: call finish_rollout() "
-                             "(compute_returns_and_advantage) first")
-        if not sink.full():
-            raise ValueError("train() needs a full sink (%d of %d steps recorded)" % (sink.steps(), sink.n_steps))
-        n = sink.obs.shape[2]
-        return 1 if granule > 1 and n % granule else int(granule)
-
-    def stats(self):
-        """The last minibatch's statistics as a dict: ONE synchronisation, and only when called."""
-        return dict(zip(STATS, self.stats_t.cpu().tolist()))
 
     # ---- the train sequence: a whole train() on device-side state ----
     def _train_state(self, sink):
@@ -296,3 +318,111 @@ class TrainGraph:
 
     def replay(self):
         self.graph.replay()
+
+
+class RecurrentPPOLearner(_Learner):
+    """The minibatch update of a ``FusedRecurrentPartner``'s ``LSTMActorCritic`` (include/oc_policy.h, last section:
+    ``oc_policy_rppo_update``): advantage normalisation, the forward over whole recorded sequences from the
+    seat's ``h0`` / ``c0`` (``seat.begin_rollout()``), the clipped loss, backpropagation through time, the norm
+    clip, Adam and the repack of the seat's three images -- six launches on the device, in place, without a
+    synchronisation, capturable.  A minibatch is a set of ENVS (int32 ``envs`` [E], repeats allowed): every env
+    brings its whole sequence of T steps, B = E T.  The learner owns what ``PPOLearner`` owns, and ``_bwd``, the
+    backward's image of Wh and [W2; wv] transposed.  ``lp_out`` / ``v_out`` (float32 [T][E], tests) receive the
+    forward.  Not here: windows shorter than the rollout, the train sequence on device-side state
+    (``shuffle="device"``, ``train_graph``, ``target_kl``, ``clip_range_vf``)."""
+
+    def __init__(self, seat, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 betas=(0.9, 0.999), eps=1e-5, max_groups=0):
+        if not isinstance(seat, FusedRecurrentPartner):
+            raise TypeError("RecurrentPPOLearner updates a gym_comm_amd.vec_env.FusedRecurrentPartner")
+        plan = (ctypes.c_int64 * 8)()
+        _lib.check(seat._L.oc_policy_rppo_plan(seat.F, seat.C, 1, 2, 0, plan), "oc_policy_rppo_plan", seat._L)
+        self._init_state(seat, RECURRENT_PARAMS, plan[3], lr, clip_range, ent_coef, vf_coef, max_grad_norm, betas, eps,
+                         max_groups)
+        self._bwd = self._zeros(self._L.oc_policy_rppo_pack_bwd_elems())
+        self.refresh()
+
+    def refresh(self):
+        """After the module's weights were changed from OUTSIDE: repack the seat's images (``seat.refresh()``)
+        and the learner's backward image, in place.  ``update`` keeps them current itself."""
+        self.seat.refresh()
+        self._bwd.copy_(torch.from_numpy(pack_lstm_bwd(self._L, self.policy)))
+
+    def plan(self, E, T):
+        """(forward / backward workgroups, weight-gradient workgroups, (t, tile) pairs per such workgroup, P,
+        scratch floats, reduction workgroups, launches, scratch floats per sample) of E sequences of T steps."""
+        plan = (ctypes.c_int64 * 8)()
+        _lib.check(self._L.oc_policy_rppo_plan(self.F, self.C, int(T), int(E), self.max_groups, plan),
+                   "oc_policy_rppo_plan", self._L)
+        return tuple(int(v) for v in plan)
+
+    def _cfg(self, sink, E):
+        T = sink.obs.shape[0]
+        self._grow_scratch(self.plan(E, T)[4])
+        seat = self.seat
+        key = (id(sink), self.max_groups, None if self.lp_out is None else self.lp_out.data_ptr(),
+               None if self.v_out is None else self.v_out.data_ptr(), seat.h0.data_ptr())
+        cfg = self._cfgs.get(key)
+        if cfg is None:
+            keep, T, n = self._sink_tensors(sink, ("obs", "timestep", "actions", "log_probs", "advantages", "returns",
+                                                   "episode_starts"))
+            if seat.h0 is None or tuple(seat.h0.shape) != (64, n):
+                raise ValueError("the seat holds no start state for %d envs: call seat.begin_rollout() before the rollout" % n)
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            cfg = _lib.RppoCfg(
+                *[t.data_ptr() for t in keep], seat.h0.data_ptr(), seat.c0.data_ptr(), n, T, self.F, self.C,
+                OBS_TYPE[sink.obs.dtype], *seat.weight_ptrs(), self._bwd.data_ptr(),
+                *[t.data_ptr() for t in self._params],
+                self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.grad_flat.data_ptr(),
+                self._scratch.data_ptr(), self.stats_t.data_ptr(), self.hyper.data_ptr(),
+                self.ent_coef, self.vf_coef, self.max_grad_norm, self.betas[0], self.betas[1], self.eps,
+                self.max_groups, ptr(self.lp_out), ptr(self.v_out))
+            cfg._keep = keep + (seat.h0, seat.c0)
+            self._cfgs[key] = cfg
+        return cfg
+
+    def _run(self, name, sink, envs):
+        if envs.dtype != torch.int32 or envs.dim() != 1 or not envs.is_contiguous() or envs.device != self.device:
+            raise ValueError("envs: a contiguous int32 [E] tensor on %s" % (self.device,))
+        if self.seat.h0 is None:
+            raise ValueError("the seat holds no start state: call seat.begin_rollout() before the rollout")
+        E = envs.numel()
+        self._check_outs(E * sink.obs.shape[0])
+        _lib.call(self._L, name, self._dev, ctypes.byref(self._cfg(sink, E)), envs.data_ptr(), E)
+
+    def update(self, sink, envs):
+        """One minibatch of whole sequences: loss, BPTT, clip, Adam, repack.  Six launches, no synchronisation.
+        The sink must be full with its slots in chronological order (``train`` checks it; here it is the
+        caller's duty)."""
+        self._run("oc_policy_rppo_update", sink, envs)
+
+    def grad(self, sink, envs):
+        """The clipped gradient (``grad_flat`` [P]; ``grads[name]`` are views of it, returned) and the
+        statistics only."""
+        self._run("oc_policy_rppo_grad", sink, envs)
+        return self.grads
+
+    def minibatches(self, sink, envs_per_batch, granule=32, generator=None):
+        """A device permutation (``torch.randperm``) of the sink's envs, cut into int32 tensors of
+        ``envs_per_batch``; ``granule=32`` shuffles tiles of 32 neighbouring envs, whose rows load coalesced.
+        A last batch whose E T would be 1 is dropped."""
+        T, _, n = sink.obs.shape
+        g = int(granule)
+        if g < 1 or n % g:
+            raise ValueError("granule %d does not divide the sink's %d envs" % (g, n))
+        perm = torch.randperm(n // g, device=self.device, generator=generator)
+        envs = (perm.unsqueeze(1) * g + torch.arange(g, device=self.device)).reshape(-1).to(torch.int32)
+        return [b for b in envs.split(int(envs_per_batch)) if b.numel() * T >= 2]
+
+    def train(self, sink, n_epochs=10, envs_per_batch=None, granule=32, generator=None):
+        """``n_epochs`` passes over a FULL fused sink whose ``finish_rollout`` has run and whose slots are in
+        chronological order (``count == n_steps``, ``pos == 0``: ``seat.begin_rollout()``, then exactly
+        ``n_steps`` steps).  ``envs_per_batch=None``: every env in one minibatch."""
+        granule = self._check_trainable(sink, granule)
+        if sink.steps() != sink.n_steps or int(sink.pos.item()) != 0:
+            raise ValueError("train() needs the sink's slots in chronological order: exactly %d steps since "
+                             "begin_rollout() (count %d, pos %d)" % (sink.n_steps, sink.steps(), int(sink.pos.item())))
+        n = sink.obs.shape[2]
+        for _ in range(int(n_epochs)):
+            for envs in self.minibatches(sink, envs_per_batch or n, granule, generator):
+                self.update(sink, envs)

@@ -127,7 +127,7 @@ class MLPActorCritic(MLPPolicy):
 
 class LSTMActorCritic(torch.nn.Module):
     """One LSTM cell of 64 units with the actor's and the critic's heads on its output: the network of
-    include/oc_policy.h's last section in plain float32, gates in ``torch.nn.LSTMCell``'s order i, f, g, o.
+    include/oc_policy.h's recurrent-seat section in plain float32, gates in ``torch.nn.LSTMCell``'s order i, f, g, o.
 
         forward(obs, state, episode_start) -> (move logits [4][n], comm logits [C][n], (h, c), value [n])
 
@@ -618,7 +618,7 @@ class FusedActorCriticPartner(_FusedSeat, _RecordingSeat):
 
 
 def pack_lstm(L, policy):
-    """An ``LSTMActorCritic``'s current weights as the three images of include/oc_policy.h's last section:
+    """An ``LSTMActorCritic``'s current weights as the three images of include/oc_policy.h's recurrent-seat section:
     numpy ``(gates, head, head_bias)``.  Host code only, as ``pack_fragments``."""
     F, C = int(policy.wx.shape[1]), int(policy.C)
     wx, wt, b, wh, w2, b2, wv, bv = (_f32(t) for t in (policy.wx, policy.wt, policy.b, policy.wh, policy.w2,
@@ -637,6 +637,16 @@ def pack_lstm(L, policy):
     return og, oh, ob
 
 
+def pack_lstm_bwd(L, policy):
+    """A recurrent learner's own image of an ``LSTMActorCritic`` (include/oc_policy.h: ``bwd``): numpy float32, Wh and
+    [W2; wv] transposed for the backward's products.  Host code only, as ``pack_fragments``."""
+    out = np.zeros(L.oc_policy_rppo_pack_bwd_elems(), np.float32)
+    rc = L.oc_policy_rppo_pack_bwd(_fp(_f32(policy.wh)), _fp(_f32(policy.w2)), _fp(_f32(policy.wv).reshape(-1)),
+                                   int(policy.C), _fp(out))
+    _lib.check(rc, "oc_policy_rppo_pack_bwd", L)
+    return out
+
+
 class FusedRecurrentPartner(_RecordingSeat):
     """An ``LSTMActorCritic`` in the seat of a recurrent player as ONE launch (include/oc_policy.h:
     ``oc_policy_lstm_ac``): the masked state, the cell (the 256 gate rows on the matrix cores, one wave = 32
@@ -651,7 +661,9 @@ class FusedRecurrentPartner(_RecordingSeat):
     The seat owns ``h``, ``c``, float32 [64][n], updated IN PLACE by the launch (a lane reads exactly the
     elements it writes); an env whose ``episode_start`` is set starts from the zero state inside the kernel.
     ``score(obs, state, episode_start, pairs)`` evaluates GIVEN actions from a GIVEN state and writes no
-    state at all: the entry a recurrent update will use."""
+    state at all.  ``begin_rollout()`` (called where ``sink.reset()`` is called otherwise) keeps the state the
+    rollout starts from in ``h0`` / ``c0``: what ``RecurrentPPOLearner`` (learner.py) unrolls the recorded
+    sequences from."""
     graph_safe = True
 
     def __init__(self, policy, sample=True, seed=None, device="cuda", sink=None, keep_logits=False):
@@ -670,12 +682,23 @@ class FusedRecurrentPartner(_RecordingSeat):
         if self.F + 2 > 64:
             raise ValueError("the fused kernel takes at most 62 observation rows (got %d)" % self.F)
         self._rng = self.episode_start = self.log_prob = self.value = self.logits = self.h = self.c = None
+        self.h0 = self.c0 = None
         self._w = None
         self.refresh()
 
     def refresh(self):
         """(Re)pack the module's current weights and upload them, in place after the first time."""
         self._w = _upload(self._w, pack_lstm(self._L, self.policy), self.device)
+
+    def weight_ptrs(self):
+        """Device addresses of the three images (gates, head, head_bias)."""
+        w = self._w
+        return w[0].data_ptr(), w[1].data_ptr(), w[2].data_ptr()
+
+    @property
+    def weight_device(self):
+        """Where the images live (``device`` with its index resolved)."""
+        return self._w[0].device
 
     def _buffers(self, n):
         if self.log_prob is None or self.log_prob.numel() != n:
@@ -686,6 +709,7 @@ class FusedRecurrentPartner(_RecordingSeat):
             self.value = torch.zeros(n, dtype=torch.float32, device=dev)
             self.h = torch.zeros((64, n), dtype=torch.float32, device=dev)
             self.c = torch.zeros((64, n), dtype=torch.float32, device=dev)
+            self.h0, self.c0 = torch.zeros_like(self.h), torch.zeros_like(self.c)
             self.logits = torch.zeros((4 + self.C, n), dtype=torch.float32, device=dev) if self.keep_logits else None
 
     def _launch(self, rows, timestep, state_in, state_out, episode_start, given, move_row, comm_row, log_prob, value):
@@ -745,6 +769,21 @@ class FusedRecurrentPartner(_RecordingSeat):
         if self.episode_start is not None:
             self.episode_start.fill_(1.0)
 
+    def begin_rollout(self, n=None):
+        """A new rollout begins with the state as it is: ``h -> h0``, ``c -> c0`` (two device copies, no
+        synchronisation) and the sink, if there is one, reset.  ``episode_start`` stays as it is.  ``n``: the
+        number of envs, for a seat that has not acted yet (its state is zero)."""
+        if self.h is None:
+            if n is None and self.sink is not None:
+                n = self.sink.obs.shape[2]
+            if n is None:
+                raise ValueError("begin_rollout before the first act_into needs the number of envs")
+            self._buffers(int(n))
+        self.h0.copy_(self.h)
+        self.c0.copy_(self.c)
+        if self.sink is not None:
+            self.sink.reset()
+
     def update(self, rewards, dones):
         """pantheonrl's ``Agent.update(reward, done)`` for the batch, on buffers that exist by now."""
         self._buffers(dones.numel())
@@ -752,10 +791,11 @@ class FusedRecurrentPartner(_RecordingSeat):
 
     def get_state(self, n):
         """The seat's mutable state: its random streams, ``episode_start``, the last ``log_prob`` / ``value``,
-        the sink's position, ``h`` and ``c``."""
+        the sink's position, ``h`` and ``c``, and the rollout's start state ``h0`` and ``c0``."""
         self._buffers(n)
         return (self._rng.clone(), self.episode_start.clone(), self.log_prob.clone(), self.value.clone(),
-                None if self.sink is None else self.sink.get_state(), self.h.clone(), self.c.clone())
+                None if self.sink is None else self.sink.get_state(), self.h.clone(), self.c.clone(),
+                self.h0.clone(), self.c0.clone())
 
     def set_state(self, st):
         self._rng.copy_(st[0])
@@ -766,3 +806,6 @@ class FusedRecurrentPartner(_RecordingSeat):
             self.sink.set_state(st[4])
         self.h.copy_(st[5])
         self.c.copy_(st[6])
+        if len(st) > 7:                      # (a 7-tuple: a state taken before h0 / c0 existed)
+            self.h0.copy_(st[7])
+            self.c0.copy_(st[8])

@@ -35,6 +35,9 @@ Partners
                            log-probability and value from one launch, recorded into a ``RolloutSink``;
                            ``PPOLearner`` (learner.py) is its update: loss, backward, clip, Adam and
                            the repack of the seat's weights in three launches per minibatch;
+  ``FusedRecurrentPartner``  an ``LSTMActorCritic`` in the seat of a recurrent player, one launch per step;
+                           ``RecurrentPPOLearner`` (learner.py) is its update over whole recorded sequences:
+                           forward, backpropagation through time, clip, Adam and the repack in six launches;
   any callable ``partner(obs_dict) -> [n, 2]`` still works (slow path).
 How a seated player yields its actions -- pairs consumed as they lie, ``act_into`` on the action
 rows, a callable -- is decided in one place, ``seat_actions``, for the partner's seat and the ego's.
@@ -65,7 +68,7 @@ from .partners import (FusedActorCriticPartner, FusedMLPPartner, FusedRecurrentP
                        LSTMActorCritic, MLPActorCritic, MLPPolicy, RandomPartner, RecurrentPolicyPartner,
                        TorchPolicyPartner)
 from .rollout import RolloutSink  # noqa: F401 (re-exported)
-from .learner import PPOLearner  # noqa: F401 (re-exported)
+from .learner import PPOLearner, RecurrentPPOLearner  # noqa: F401 (re-exported)
 
 try:                                                    # pragma: no cover - SB3 absent in CI image
     from stable_baselines3.common.vec_env import VecEnv as _VecEnvBase

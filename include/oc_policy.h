@@ -329,8 +329,8 @@ OC_API int oc_policy_ppo_train_step(const oc_ppo_cfg *cfg, const oc_ppo_train *t
  * What it stands in for: the forward of the RECURRENT learner the reference seats on both sides of the
  * env (trainer.py:92-112: RecurrentPPO('MultiInputPolicy', ...), for the partner inside OnPolicyAgent) --
  * one LSTM cell of 64 units shared by actor and critic, its state kept per env and put back to zero
- * where an episode starts.  OUT OF SCOPE: the update (backpropagation through time), hidden sizes other
- * than 64, a separate critic LSTM.
+ * where an episode starts.  OUT OF SCOPE: hidden sizes other than 64, a separate critic LSTM.  (The update,
+ * backpropagation through time: the last section of this header.)
  *
  * The network (gym-comm_amd/partners.py: LSTMActorCritic), per env, H = 64, F observation rows x, gates
  * in torch.nn.LSTMCell's order i, f, g, o:
@@ -412,6 +412,119 @@ OC_API int oc_policy_lstm_pack_head_bias(const float *b2, const float *bv, int32
  * h_in / c_in, move_row and comm_row together.  Never allocates or synchronises; capturable. */
 OC_API int oc_policy_lstm_ac(const oc_policy_lstm_player *pl, const double *timestep, int32_t F, int32_t C,
                              int32_t obs_type, int64_t n, void *stream);
+
+/* ---- the recurrent seat's PPO update: forward over whole sequences, BPTT, clip, Adam, repack ----------
+ *
+ * What it restates: one minibatch of train() of the reference's RecurrentPPO (trainer.py:92-112 seats it) for
+ * the network of the section above: advantage normalisation, the forward over whole recorded sequences, the
+ * clipped loss, the gradient through time, the norm clip, Adam, and the repack of the seat's three images in
+ * place.  OUT OF SCOPE:
+ *   - truncated windows shorter than the rollout, and states recorded mid-rollout
+ *   - the train sequence (device shuffle, target_kl, clip_range_vf, train_graph) for the recurrent learner
+ *   - the marginal-regularisation term
+ *   - hidden sizes other than 64
+ *   - a separate critic LSTM
+ *   - the cell inside the step kernel
+ *
+ * Sequences.  A sequence is one env over the whole sink: steps t = 0 .. T - 1 in slots 0 .. T - 1 of tensors
+ * shaped as an oc_rollout_buf's (obs [T][F][n], timestep double [T][n], actions int32 [T][2][n], log_probs /
+ * advantages / returns / episode_starts float [T][n]).  It is the CALLER's duty that the buffer is full with
+ * count == T and pos == 0, so that slot order is chronological.  A minibatch is envs, int32 [E], E >= 1 and
+ * E T >= 2; any order, repeats allowed; sample (t, e) is slot t of env envs[e].  An index outside 0 .. n - 1 is
+ * a caller error and is NOT checked on the device.  B = E T is the divisor everywhere oc_policy_ppo_update uses B.
+ *
+ * Forward.  The start state is (h0, c0), float [64][n]: the seat's state before the first step of the rollout,
+ * a constant in the gradient.  Step t applies exactly the network of the section above to the running state
+ * with episode_starts[t] as its select -- oc_policy_lstm_ac's arithmetic in `given` mode, operation for
+ * operation; the state is float32 and is fed back as fp16(h) -- so lp_out / v_out (optional, float [T][E]) are
+ * bit for bit what T successive scoring launches return, each carrying the state the previous one produced.
+ *
+ * Loss.  oc_policy_ppo_update's over the B samples: A^ from the mean and the UNBIASED std of the B gathered
+ * advantages (+ 1e-8), rho = exp(lp - old_lp), the clipped policy term, the value loss without value clipping,
+ * the entropy term.  A recorded action outside its head's range makes lp = -inf: that sample contributes
+ * nothing to any loss term and is counted in `bad`; B stays the divisor.  The same ten stats are written.
+ *
+ * Gradient.  With respect to the fp32 master weights, flat [P] in this order: wx [256][F], wt [256], b [256],
+ * wh [256][64], w2 [4 + C][64], b2 [4 + C], wv [64], bv [1]; P = 256 (F + 2) + 16384 + 65 (4 + C) + 65.  It is
+ * evaluated at the network the images represent, as oc_policy_ppo_update's is: the folded fp16 gate and head
+ * weights divided back by their fold constants, fp16 features and fp16(h) in the products, the roundings not
+ * differentiated.  Behind the forward everything is float32 with fp32-operand matrix products.  The
+ * activations' derivatives come from the unrounded r values: i, f, o = r(a) gives sigma' = r (1 - r); g = 1 - 2 r
+ * gives tanh' = 4 r (1 - r); tanh(c) uses its own r.  Per step, going backwards, with D_t = d (B loss) / d
+ * [logits; value] as in the MLP section and dh_next, dc_next zero behind the last step:
+ *     dh   = [W2; wv]^T D_t + dh_next
+ *     do   = dh tanh(c_t)
+ *     dc   = dc_next + dh o (1 - tanh^2(c_t))
+ *     dz_i = dc g i (1 - i);  dz_f = dc c_in f (1 - f);  dz_g = dc i (1 - g^2);  dz_o = do o (1 - o)
+ *     gWx += dz x^T;  gwt += dz ts;  gb += sum dz;  gWh += dz h_in^T;  gW2 += D h_t^T;  gb2, gwv, gbv likewise
+ *     dh_next = s_t ? 0 : Wh^T dz;    dc_next = s_t ? 0 : dc f
+ * c_in and h_in are the values after the select; s_t is a select by episode_starts[t] > 0: the start cuts the
+ * gradient (and a NaN or an infinity in a starting env's h0 / c0 reaches nothing).  The 1 / B is applied to
+ * the summed gradient in float32.
+ *
+ * Against the float64 restatement with the same roundings (tests/recurrent_ppo_ref.py) the clipped gradient
+ * lies within TOL_G of each tensor's largest element and the statistics within TOL_S; both constants are 4 x
+ * the largest difference seen on an MI355X over the test's three cases -- measured, not a bound; the figures
+ * are in tests/recurrent_ppo_ref.py.
+ *
+ * Clip, Adam, repack.  clip_grad_norm_ with the norm in double, in a fixed order; Adam as in
+ * oc_policy_ppo_update (m, v [P] and the int32 step on the device, hyper = (lr, clip_range) read on the device).
+ * Afterwards gates, head and head_bias are rewritten IN PLACE, bit for bit what oc_policy_lstm_pack_gates /
+ * _head / _head_bias produce from the same fp32 weights, and so is `bwd`, the learner's own image, float
+ * [oc_policy_rppo_pack_bwd_elems()]: first Wh^T, float [2][8][16][64], element (m, u, q, l) = the fp16 value of
+ * the folded Wh[64 (u >> 1) + 32 (u & 1) + (q & 3) + 8 (q >> 2) + 4 (l >> 5)][32 m + (l & 31)] times the inverse
+ * of its fold (-ln 2; ln 2 / 2 for gate g), one float32 product -- Wh transposed and k-permuted to the order
+ * in which d z sits in the gate product's accumulators; then [W2; wv]^T in w2t's layout (float [2][16][64],
+ * oc_policy_ppo_update's section) holding the fp16 value of log2(e) W times ln 2.
+ *
+ * Determinism: no floating-point atomics; workgroups write partials and one kernel sums them in a fixed
+ * order: the same call gives the same bits.  Six launches, whatever (T, E, F, C, max_groups) are; none
+ * allocates or synchronises; all are capturable:
+ *   1. the advantage statistics (double, an order fixed by B)
+ *   2. the forward: one wave per 32 sequences, t ascending, the state in registers; leaves per sample the
+ *      gates, h, c and D in `scratch` (416 floats per sample) and per workgroup the loss sums
+ *   3. the backward: the same mapping, t descending; overwrites the gates with d z
+ *   4. the weight gradients: products over samples, parallel over (t, tile of 32 sequences); partials [Gw][P]
+ *   5. the partials summed over g ascending, times 1 / B; the squared norm's partial sums in double
+ *   6. one workgroup: the norm, the clip, the statistics and (oc_policy_rppo_update) Adam and the repack */
+typedef struct {
+  const void *obs;            /* the rollout tensors (above) */
+  const double *timestep;
+  const int32_t *actions;
+  const float *log_probs, *advantages, *returns, *episode_starts;
+  const float *h0, *c0;       /* float [64][n]: the state before the rollout's first step */
+  int64_t n;
+  int32_t T, F, C, obs_type;  /* obs_type: 0 int32, 1 int8, 2 float32 */
+  uint16_t *gates, *head;     /* the seat's three images: read by the forward, rewritten by oc_policy_rppo_update */
+  float *head_bias;
+  float *bwd;                 /* float [oc_policy_rppo_pack_bwd_elems()], the learner's (above) */
+  float *p_wx, *p_wt, *p_b, *p_wh, *p_w2, *p_b2, *p_wv, *p_bv;   /* fp32 master weights (oc_policy_rppo_update only) */
+  float *m, *v;               /* Adam state, float [P] each (oc_policy_rppo_update only) */
+  int32_t *step;              /* int32 [1], Adam's step counter (oc_policy_rppo_update only) */
+  float *grad;                /* out: the clipped gradient, float [P] */
+  float *scratch;             /* float [plan[4]], 8-byte aligned */
+  float *stats;               /* float [10] */
+  const float *hyper;         /* float [2] on the device: lr, clip_range */
+  float ent_coef, vf_coef, max_grad_norm, beta1, beta2, eps;
+  int32_t max_groups;         /* 0 = the library's choice (256); otherwise a cap on the weight-gradient workgroups */
+  float *lp_out, *v_out;      /* optional out, float [T][E]: the forward's log_prob and value */
+} oc_rppo_cfg;
+
+/* No device work: plan, int64 [8] (the scratch can pass 2^31 floats) = (workgroups of the forward and the
+ * backward = ceil(E / 32); workgroups Gw of the weight-gradient kernel = min(T ceil(E / 32), cap); (t, tile)
+ * pairs per such workgroup; P; floats of scratch; workgroups of the reduction; launches per call; floats of
+ * scratch per sample). */
+OC_API int oc_policy_rppo_plan(int32_t F, int32_t C, int32_t T, int32_t E, int32_t max_groups, int64_t *plan);
+
+/* Host-side packing of `bwd` (above): wh [256][64], w2 [4 + C][64], wv [64]  ->  out fp32 [_elems()]. */
+OC_API int32_t oc_policy_rppo_pack_bwd_elems(void);
+OC_API int oc_policy_rppo_pack_bwd(const float *wh, const float *w2, const float *wv, int32_t C, float *out);
+
+/* One minibatch update (6 launches), or the same launches without Adam and the repack (oc_policy_rppo_grad:
+ * leaves the clipped gradient and the statistics).  Checked before any device work: F >= 1, F + 2 <= 64,
+ * 1 <= C <= 16, T >= 1, E >= 1, 2 <= E T < 2^31, obs_type, T n < 2^31, 64 n < 2^31, non-NULL pointers. */
+OC_API int oc_policy_rppo_update(const oc_rppo_cfg *cfg, const int32_t *envs, int32_t E, void *stream);
+OC_API int oc_policy_rppo_grad(const oc_rppo_cfg *cfg, const int32_t *envs, int32_t E, void *stream);
 
 #ifdef __cplusplus
 }
