@@ -3,9 +3,12 @@
 launch per step (`oc_policy_lstm_ac`), recording into a fused `RolloutSink` from a closed loop captured as one
 hipGraph per 16 steps; then GAE in one launch and the PPO update over whole recorded sequences --
 backpropagation through time, clip, Adam and the repack of the seat's weights -- in six launches per minibatch
-(`RecurrentPPOLearner`, include/oc_policy.h: `oc_policy_rppo_update`).
+(`RecurrentPPOLearner`, include/oc_policy.h: `oc_policy_rppo_update`).  With `--graph` the whole train() -- the
+epochs' shuffles of the envs, the minibatches, the KL stop, value clipping, the logged means -- is ONE captured
+graph (`train_graph`, `oc_policy_recurrent_train_step`), replayed once per round.
 
     python examples/train_recurrent_ppo.py --envs 4096 --rounds 4
+    python examples/train_recurrent_ppo.py --envs 4096 --rounds 4 --graph --target-kl 0.03 --clip-range-vf 0.2
 """
 import argparse
 import os
@@ -28,6 +31,9 @@ def main():
     p.add_argument("--n-steps", type=int, default=128)
     p.add_argument("--epochs", type=int, default=4)
     p.add_argument("--envs-per-batch", type=int, default=1024)
+    p.add_argument("--graph", action="store_true", help="replay one captured train_graph per round; print train_stats()")
+    p.add_argument("--target-kl", type=float, default=None, help="no epoch after one whose mean approx_kl exceeds 1.5 x this")
+    p.add_argument("--clip-range-vf", type=float, default=None, help="value clipping around the recorded value")
     a = p.parse_args()
     if a.n_steps % 16:
         p.error("--n-steps is a multiple of 16 (the closed loop replays 16 steps at a time)")
@@ -38,7 +44,9 @@ def main():
     pol = LSTMActorCritic(venv._b.S, C, seed=1).cuda()
     sink = RolloutSink(a.n_steps, a.envs, venv._b.F, obs_dtype=torch.float32, fused=True)
     venv.partner = seat = FusedRecurrentPartner(pol, sample=True, seed=7, sink=sink)
-    learner = RecurrentPPOLearner(seat, lr=3e-4, ent_coef=0.01)
+    learner = RecurrentPPOLearner(seat, lr=3e-4, ent_coef=0.01, clip_range_vf=a.clip_range_vf, target_kl=a.target_kl)
+    device = a.graph or a.target_kl is not None or a.clip_range_vf is not None    # both live in the train sequence
+    graph = None
     venv.reset_tensors()
     loop = venv.closed_loop(None, steps=16)          # the ego's action rows stay as they are (all zeros)
     for r in range(a.rounds):
@@ -48,9 +56,21 @@ def main():
         for _ in range(a.n_steps // 16):
             loop.step()
         seat.finish_rollout(gamma=0.99, gae_lambda=0.95)
-        learner.train(sink, n_epochs=a.epochs, envs_per_batch=a.envs_per_batch)
+        if a.graph:
+            if graph is None:                        # the first full, finished sink: checked here, captured once
+                graph = learner.train_graph(sink, a.epochs, envs_per_batch=a.envs_per_batch, seed=r)
+            graph.replay()
+        else:
+            learner.train(sink, n_epochs=a.epochs, envs_per_batch=a.envs_per_batch, shuffle="device" if device else "torch",
+                          seed=r)
         stats = learner.stats()                      # the round's one synchronisation
         dt = time.perf_counter() - t0
+        if device:
+            ts = learner.train_stats()
+            print("round %d: train_stats: %d updates in %d epochs%s; means: loss %.4f policy %.4f value %.4f entropy %.4f "
+                  "kl %.5f clip %.3f" % (r, ts["updates"], ts["epochs"], " (stopped by target_kl)" if ts["stopped"] else "",
+                                         ts["loss"], ts["policy_loss"], ts["value_loss"], ts["entropy_loss"], ts["approx_kl"],
+                                         ts["clip_fraction"]))
         print("round %d: %.1f ms; mean reward %.4f; last minibatch: loss %.4f policy %.4f value %.4f entropy %.4f "
               "kl %.5f clip %.3f |g| %.3f bad %d"
               % (r, dt * 1e3, sink.rewards.mean().item(), stats["loss"], stats["policy_loss"], stats["value_loss"],

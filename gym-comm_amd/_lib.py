@@ -187,6 +187,8 @@ def _libs_table():
             "oc_policy_rppo_pack_bwd": (cint, [fp, fp, fp, i32, fp]),
             "oc_policy_rppo_update": (cint, [P(RppoCfg), vp, i32, vp]),
             "oc_policy_rppo_grad": (cint, [P(RppoCfg), vp, i32, vp]),
+            # ... and its step of the train sequence (between oc_policy_ppo_train_begin / _epoch_begin)
+            "oc_policy_recurrent_train_step": (cint, [P(RppoCfg), P(PpoTrain), vp, i32, vp]),
         }),
         "hostio": Lib("OC_HOSTIO_LIB", "oc_hostio_abi_version", 1, "oc_hostio_last_error", {
             "oc_hostio_abi_version": (cint, None),

@@ -508,6 +508,14 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_ppo_finish(const PpoArgs
 // the checks of one minibatch, made before any device work (oc_policy_ppo.hip); plan as oc_policy_ppo_plan's
 int ppo_check(const char *who, const oc_ppo_cfg *c, const int32_t *idx, int32_t B, bool apply, int32_t *plan);
 
+// the train state's pointers (oc_policy_train.hip, oc_policy_rtrain.hip)
+inline int train_check(const char *who, const oc_ppo_train *t) {
+  if (!t) return fail("%s: bad argument (train)", who);
+  if (!t->values || !t->hyper_ext || !t->ctl || !t->acc)
+    return fail("%s: a NULL pointer among the train state's values, hyper_ext, ctl, acc", who);
+  return 0;
+}
+
 // after a unit's launches: 0, or the launch error, recorded under the entry point's name
 inline int ppo_launched(const char *who) {
   const hipError_t e = hipGetLastError();

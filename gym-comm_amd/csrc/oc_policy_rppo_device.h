@@ -1,6 +1,8 @@
-// oc_policy_rppo_device.h -- the kernels of the recurrent PPO update (include/oc_policy.h, last section:
-// oc_policy_rppo_update, oc_policy_rppo_grad) for the fused recurrent seat.  Included by oc_policy_rppo.hip
-// only.  gfx950 only.
+// oc_policy_rppo_device.h -- the kernels of the recurrent PPO update (include/oc_policy.h, the recurrent update's section:
+// oc_policy_rppo_update, oc_policy_rppo_grad) for the fused recurrent seat, and -- the same templates with
+// TRAIN = true -- of a step of the recurrent learner's train sequence (oc_policy_recurrent_train_step).  Included
+// through oc_policy_rppo_host.h by oc_policy_rppo.hip, which instantiates the TRAIN = false kernels only, and by
+// oc_policy_rtrain.hip, which instantiates the TRAIN = true ones only.  gfx950 only.
 //
 // Six launches per minibatch of E sequences of T steps (B = E T samples), all sized at launch:
 //
@@ -31,6 +33,12 @@
 //                    parameters tid, tid + 1024, ...
 //
 // No loop's trip count depends on data; no workgroup waits on another.
+//
+// TRAIN = true: every kernel returns at once, having written nothing, when the train sequence is halted
+// (ppo_halted: ctl.stop or ctl.error) -- a wave-uniform test at the very top, before any LDS use or barrier;
+// k_rppo_forward clips the value prediction around the recorded value where hyper_ext[0] > 0; k_rppo_finish adds
+// the minibatch's statistics to the epoch's and the train's sums.  TRAIN = false takes the arguments, and compiles
+// to the code, it had before the variants existed: RppoArgs<false> and RppoOut<false> add no member.
 #ifndef OC_POLICY_RPPO_DEVICE_H
 #define OC_POLICY_RPPO_DEVICE_H
 #include "../../include/oc_policy.h"
@@ -48,6 +56,24 @@ constexpr int RPPO_REDUCE_THREADS = 256;
 constexpr int RPPO_SAMPLE_FLOATS = 256 + 64 + 64 + 32;   // scratch per sample: gates / d z, h, c, D
 constexpr int RPPO_DEFAULT_GROUPS = 256;              // the weight-gradient kernel's cap where max_groups == 0
 constexpr float RPPO_K_TANH = 2.0f * K_LOG2E;         // k_policy_lstm's K_TANH
+
+// the kernels' arguments: the update's alone, or with the train sequence's device state behind them
+template <bool TRAIN>
+struct RppoArgs : oc_rppo_cfg {};
+template <>
+struct RppoArgs<true> : oc_rppo_cfg {
+  oc_ppo_train tr;
+};
+// the output of a kernel that takes no cfg (k_rppo_adv: stats; k_rppo_reduce: grad), with the control words behind it
+template <bool TRAIN>
+struct RppoOut {
+  float *to;
+};
+template <>
+struct RppoOut<true> {
+  float *to;
+  const int32_t *ctl;
+};
 
 // where the regions of `scratch` begin (the plan's arithmetic, made once on the host)
 struct RppoScratch {
@@ -82,8 +108,14 @@ __device__ __forceinline__ _Float16 rppo_fold(float w, float scale) {
 }
 
 // ---- a. advantage statistics: sample i is step i / E of env envs[i % E] --------------------------------
+template <bool TRAIN = false>
 __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_rppo_adv(const float *adv, const int32_t *envs, const int E,
-                                                                const int B, const uint32_t n32, float *stats) {
+                                                                const int B, const uint32_t n32,
+                                                                const RppoOut<TRAIN> out) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(out.ctl)) return;   // uniform
+  }
+  float *stats = out.to;
   __shared__ double red[PPO_FINISH_THREADS];
   const int tid = threadIdx.x;
   double s = 0.0;
@@ -99,9 +131,12 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_rppo_adv(const float *ad
 }
 
 // ---- b. the forward over whole sequences, the loss and D ------------------------------------------------
-template <int OT>
-__global__ void __launch_bounds__(64) k_rppo_forward(const oc_rppo_cfg p, const int32_t *envs, const int E,
+template <int OT, bool TRAIN = false>
+__global__ void __launch_bounds__(64) k_rppo_forward(const RppoArgs<TRAIN> p, const int32_t *envs, const int E,
                                                      const RppoScratch sc) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(p.tr.ctl)) return;   // uniform
+  }
   __shared__ float sums[64 * RPPO_SUMS];
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
   const int e0 = (int)blockIdx.x * 32 + r;
@@ -113,6 +148,9 @@ __global__ void __launch_bounds__(64) k_rppo_forward(const oc_rppo_cfg p, const 
   const half8 *wg = (const half8 *)p.gates + lane;
   const float mean = p.stats[6], denom = p.stats[7] + 1e-8f, clip = p.hyper[1];
   const float lo = 1.0f - clip, hi = 1.0f + clip;
+  float cvf = 0.0f;                      // clip_range_vf; <= 0 (or NaN): no value clipping
+  if constexpr (TRAIN) cvf = p.tr.hyper_ext[0];
+  const bool vclip = cvf > 0.0f;         // uniform
 
   float hst[2][16], cst[2][16];   // the running state: unit 32 m + acc_row(q, h) in [m][q]
 #pragma unroll
@@ -129,6 +167,12 @@ __global__ void __launch_bounds__(64) k_rppo_forward(const oc_rppo_cfg p, const 
     const size_t base = (size_t)t * (size_t)F * n + env;
     const float ts = (float)p.timestep[smp];
     const bool start = p.episode_starts[smp] > 0.0f;
+    // value clipping (TRAIN): the recorded value is asked for here, ahead of the products, and only where it is
+    // used -- at the point of use its latency would stand exposed in every one of the T steps
+    float oldv = 0.0f;
+    if constexpr (TRAIN) {
+      if (vclip) oldv = p.tr.values[smp];   // uniform
+    }
     float cin[2][16];
 #pragma unroll
     for (int m = 0; m < 2; m++)
@@ -270,12 +314,22 @@ __global__ void __launch_bounds__(64) k_rppo_forward(const oc_rppo_cfg p, const 
       const float v = glp * ((c == a ? 1.0f : 0.0f) - pr[c]) + p.ent_coef * (pr[c] * (lnp[c] + H));
       d[c] = (ok && c < count) ? v : 0.0f;
     }
-    if (h == 0 && ok) d[4] = 2.0f * p.vf_coef * (val - ret);
+    // value clipping (TRAIN), as k_ppo_grad's: the prediction moves at most cvf from the recorded value, and the
+    // gradient passes where it has not been cut (the ends included, as torch's clamp backward does)
+    // (selects on the value loaded at the top of the step: no branch, and no load, in the step's tail)
+    float vp = val;
+    bool vopen = true;
+    if constexpr (TRAIN) {
+      const float dv = val - oldv;
+      vp = vclip ? oldv + fminf(fmaxf(dv, -cvf), cvf) : val;
+      vopen = !vclip || (dv >= -cvf && dv <= cvf);
+    }
+    if (h == 0 && ok) d[4] = vopen ? 2.0f * p.vf_coef * (vp - ret) : 0.0f;
     if (ok) {
       s_ent -= H;
       if (h == 0) {
         s_pol -= fminf(t1, t2);
-        s_val += (ret - val) * (ret - val);
+        s_val += (ret - vp) * (ret - vp);
         s_kl += old - lp_sum;
         s_clip += fabsf(ratio - 1.0f) > clip ? 1.0f : 0.0f;
       }
@@ -301,8 +355,12 @@ __global__ void __launch_bounds__(64) k_rppo_forward(const oc_rppo_cfg p, const 
 }
 
 // ---- c. backpropagation through time ----------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_rppo_backward(const oc_rppo_cfg p, const int32_t *envs, const int E,
+template <bool TRAIN = false>
+__global__ void __launch_bounds__(64) k_rppo_backward(const RppoArgs<TRAIN> p, const int32_t *envs, const int E,
                                                       const RppoScratch sc) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(p.tr.ctl)) return;   // uniform
+  }
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
   const int e0 = (int)blockIdx.x * 32 + r;
   const bool valid = e0 < E;
@@ -384,9 +442,12 @@ __global__ void __launch_bounds__(64) k_rppo_backward(const oc_rppo_cfg p, const
 }
 
 // ---- d. the weight gradients: products over samples ------------------------------------------------------------
-template <int OT>
-__global__ void __launch_bounds__(256) k_rppo_wgrad(const oc_rppo_cfg p, const int32_t *envs, const int E, const int tiles,
-                                                    const int per, const RppoScratch sc) {
+template <int OT, bool TRAIN = false>
+__global__ void __launch_bounds__(256) k_rppo_wgrad(const RppoArgs<TRAIN> p, const int32_t *envs, const int E,
+                                                    const int tiles, const int per, const RppoScratch sc) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(p.tr.ctl)) return;   // uniform over the four waves: none reaches a barrier
+  }
   __shared__ float L[RPPO_ROWS * RPPO_STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
   const int col_ = tid & 31, grp = tid >> 5;             // staging: a thread fills column col_ of rows grp, grp + 8, ...
@@ -485,8 +546,13 @@ __global__ void __launch_bounds__(256) k_rppo_wgrad(const oc_rppo_cfg p, const i
 }
 
 // ---- e. reduce, clip, statistics; Adam and the repack ----------------------------------------------------------
+template <bool TRAIN = false>
 __global__ void __launch_bounds__(RPPO_REDUCE_THREADS) k_rppo_reduce(const RppoScratch sc, const int G, const int P,
-                                                                    const float fB, float *grad) {
+                                                                    const float fB, const RppoOut<TRAIN> out) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(out.ctl)) return;   // uniform
+  }
+  float *grad = out.to;
   __shared__ double red[RPPO_REDUCE_THREADS];
   const int tid = threadIdx.x, pi = (int)blockIdx.x * RPPO_REDUCE_THREADS + tid;
   float s = 0.0f;
@@ -504,9 +570,12 @@ __global__ void __launch_bounds__(RPPO_REDUCE_THREADS) k_rppo_reduce(const RppoS
   if (tid == 0) sc.sq[blockIdx.x] = red[0];
 }
 
-template <bool APPLY>
-__global__ void __launch_bounds__(PPO_FINISH_THREADS) k_rppo_finish(const oc_rppo_cfg p, const int B, const int Gf,
+template <bool APPLY, bool TRAIN = false>
+__global__ void __launch_bounds__(PPO_FINISH_THREADS) k_rppo_finish(const RppoArgs<TRAIN> p, const int B, const int Gf,
                                                                    const int Gr, const RppoScratch sc) {
+  if constexpr (TRAIN) {
+    if (ppo_halted(p.tr.ctl)) return;   // uniform
+  }
   __shared__ double red[PPO_FINISH_THREADS];
   const int tid = threadIdx.x, F = p.F, C = p.C;
   const RppoLayout lay(F, C);
@@ -525,6 +594,17 @@ __global__ void __launch_bounds__(PPO_FINISH_THREADS) k_rppo_finish(const oc_rpp
     p.stats[3] = (float)(s[3] / B), p.stats[4] = (float)(s[4] / B), p.stats[5] = norm;
     p.stats[8] = (float)s[5];
     p.stats[9] = (float)(pol + (double)p.ent_coef * ent + (double)p.vf_coef * val);
+    if constexpr (TRAIN) {
+      // the float values just written, added in double by this one thread (k_ppo_finish's accounting): the
+      // same sequence of minibatches gives the same sums, bit for bit
+      double *acc = p.tr.acc;
+      acc[OC_PPO_ACC_EPOCH_KL] += (double)p.stats[3];
+      acc[OC_PPO_ACC_EPOCH_COUNT] += 1.0;
+      acc[OC_PPO_ACC_SUMS + 0] += (double)p.stats[0], acc[OC_PPO_ACC_SUMS + 1] += (double)p.stats[1];
+      acc[OC_PPO_ACC_SUMS + 2] += (double)p.stats[2], acc[OC_PPO_ACC_SUMS + 3] += (double)p.stats[3];
+      acc[OC_PPO_ACC_SUMS + 4] += (double)p.stats[4], acc[OC_PPO_ACC_SUMS + 5] += (double)p.stats[9];
+      p.tr.ctl[OC_PPO_CTL_UPDATES] += 1;
+    }
   }
   int step = 0;
   float step_size = 0.0f, bc2s = 1.0f;

@@ -55,13 +55,6 @@ __global__ void __launch_bounds__(PERM_THREADS) k_ppo_perm(const oc_ppo_train t,
   }
 }
 
-int train_check(const char *who, const oc_ppo_train *t) {
-  if (!t) return fail("%s: bad argument (train)", who);
-  if (!t->values || !t->hyper_ext || !t->ctl || !t->acc)
-    return fail("%s: a NULL pointer among the train state's values, hyper_ext, ctl, acc", who);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {

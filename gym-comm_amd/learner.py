@@ -1,7 +1,8 @@
 """``PPOLearner``: the PPO update of a ``FusedActorCriticPartner``'s ``MLPActorCritic`` as three
 launches per minibatch (include/oc_policy.h: ``oc_policy_ppo_update``); ``RecurrentPPOLearner``: the update of a
 ``FusedRecurrentPartner``'s ``LSTMActorCritic`` over whole recorded sequences, six launches per minibatch
-(``oc_policy_rppo_update``) -- see ``vec_env`` for the overview."""
+(``oc_policy_rppo_update``).  Both run a whole ``train()`` on device-side state as well (``shuffle="device"``,
+``train_graph``: the train sequence of include/oc_policy.h) -- see ``vec_env`` for the overview."""
 import ctypes
 
 import torch
@@ -19,8 +20,9 @@ RECURRENT_PARAMS = ("wx", "wt", "b", "wh", "w2", "b2", "wv", "bv")   # the order
 
 class _Learner:
     """What the two learners share: the checked master weights, Adam's state, the flat gradient with its views,
-    the statistics, the device-side hyper-parameters, the scratch that regrows by retiring, and the checks of
-    a sink before ``train()``."""
+    the statistics, the device-side hyper-parameters, the scratch that regrows by retiring, the checks of
+    a sink before ``train()``, and the train sequence's device state (include/oc_policy.h: ``oc_ppo_train``) with
+    what reads and captures it: ``set_clip_range_vf`` / ``set_target_kl``, ``train_stats``, ``train_graph``'s body."""
 
     def _init_state(self, seat, names, P, lr, clip_range, ent_coef, vf_coef, max_grad_norm, betas, eps, max_groups):
         pol = seat.policy
@@ -53,6 +55,16 @@ class _Learner:
         self._cfgs = {}
         self.lp_out = self.v_out = None          # set to float tensors to receive the forward (tests)
 
+    def _init_train_state(self, clip_range_vf, target_kl):
+        """The train sequence's device state (include/oc_policy.h: oc_ppo_train); 0 = off."""
+        z, dev = self._zeros, self.device
+        self.hyper_ext = torch.tensor([clip_range_vf or 0.0, target_kl or 0.0], dtype=torch.float32, device=dev)
+        # (ctl and acc are views of one buffer: train_stats() fetches both with one copy)
+        self._train_words = z(_lib.PPO_ACC["words"] + _lib.PPO_CTL["words"] // 2, torch.float64)
+        self.acc = self._train_words[:_lib.PPO_ACC["words"]]
+        self.ctl = self._train_words[_lib.PPO_ACC["words"]:].view(torch.int32)
+        self._idx, self._trains = None, {}
+
     def _zeros(self, n, dt=torch.float32):
         return torch.zeros(n, dtype=dt, device=self.device)
 
@@ -83,6 +95,15 @@ class _Learner:
     def set_clip_range(self, clip_range):
         self.hyper[1] = float(clip_range)
 
+    def set_clip_range_vf(self, clip_range_vf):
+        """Value clipping of the train sequence (``shuffle="device"``, ``train_graph``); None = off."""
+        self.hyper_ext[0] = float(clip_range_vf or 0.0)
+
+    def set_target_kl(self, target_kl):
+        """The train sequence's early stop: no epoch after one whose mean approx_kl exceeds
+        1.5 ``target_kl``; None = off."""
+        self.hyper_ext[1] = float(target_kl or 0.0)
+
     def _check_outs(self, B):
         for t in (self.lp_out, self.v_out):
             if t is not None and (t.dtype != torch.float32 or t.numel() < B or not t.is_contiguous()):
@@ -103,6 +124,59 @@ class _Learner:
     def stats(self):
         """The last minibatch's statistics as a dict: ONE synchronisation, and only when called."""
         return dict(zip(STATS, self.stats_t.cpu().tolist()))
+
+    # ---- the train sequence: a whole train() on device-side state ----
+    def _train_state(self, sink):
+        tr = self._trains.get(id(sink))
+        if tr is None:
+            v = getattr(sink, "values", None)
+            if v is None or v.device != self.device or v.dtype != torch.float32 or not v.is_contiguous() \
+                    or v.shape != sink.advantages.shape:
+                raise ValueError("the sink's values: a contiguous float32 [T][n] tensor on %s" % (self.device,))
+            tr = _lib.PpoTrain(v.data_ptr(), self.hyper_ext.data_ptr(), self.ctl.data_ptr(), self.acc.data_ptr())
+            tr._keep = (v,)
+            self._trains[id(sink)] = tr
+        return tr
+
+    def _index_buffer(self, total):
+        """The learner's own index buffer of at least ``total`` int32; regrows by retiring, as the scratch does."""
+        if self._idx is None or self._idx.numel() < total:
+            self._retired.append(self._idx)               # a captured graph may still write to it
+            self._idx = torch.zeros(total, dtype=torch.int32, device=self.device)
+        return self._idx
+
+    def _capture(self, sink, sequence):
+        """``train_graph``'s body: ``sequence(n_epochs)`` runs once eagerly for one epoch (every kernel is loaded,
+        the index buffer and the scratch are sized), the learner's state is put back, and the capture of
+        ``sequence(None)`` -- the caller's number of epochs -- follows."""
+        with _lib.on_device(self._dev):
+            state = self._train_tensors()
+            saved = [t.clone() for t in state]
+            sequence(1)
+            torch.cuda.synchronize(self.device)
+            with torch.no_grad():
+                for t, s in zip(state, saved):
+                    t.copy_(s)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                sequence(None)
+        return TrainGraph(self, sink, graph)
+
+    def train_stats(self):
+        """The reference's logged means over the updates APPLIED in the last train sequence -- policy_loss,
+        value_loss, entropy_loss, approx_kl, clip_fraction, loss -- with ``updates``, ``epochs`` (completed)
+        and ``stopped`` (by the KL rule).  ONE synchronisation, and only when called."""
+        host = self._train_words.cpu()
+        na = _lib.PPO_ACC["words"]
+        acc, ctl = host[:na].tolist(), host[na:].view(torch.int32).tolist()
+        if ctl[_lib.PPO_CTL["error"]]:
+            raise _lib.OcError("the train sequence halted: a permutation walk reached its cap (include/oc_policy.h)")
+        updates = ctl[_lib.PPO_CTL["updates"]]
+        out = {k: (acc[_lib.PPO_ACC["sums"] + i] / updates if updates else float("nan"))
+               for i, k in enumerate(TRAIN_STATS)}
+        out.update(updates=updates, stopped=bool(ctl[_lib.PPO_CTL["stop"]]),
+                   epochs=ctl[_lib.PPO_CTL["epochs"]] + (1 if acc[_lib.PPO_ACC["epoch_count"]] > 0 else 0))
+        return out
 
 
 class PPOLearner(_Learner):
@@ -127,15 +201,8 @@ class PPOLearner(_Learner):
         plan = (ctypes.c_int32 * 4)()
         _lib.check(seat._L.oc_policy_ppo_plan(seat.F, seat.C, 2, 0, plan), "oc_policy_ppo_plan", seat._L)
         self._init_state(seat, PARAMS, plan[2], lr, clip_range, ent_coef, vf_coef, max_grad_norm, betas, eps, max_groups)
-        z, dev = self._zeros, self.device
-        # the train sequence's device state (include/oc_policy.h: oc_ppo_train); 0 = off
-        self.hyper_ext = torch.tensor([clip_range_vf or 0.0, target_kl or 0.0], dtype=torch.float32, device=dev)
-        # (ctl and acc are views of one buffer: train_stats() fetches both with one copy)
-        self._train_words = z(_lib.PPO_ACC["words"] + _lib.PPO_CTL["words"] // 2, torch.float64)
-        self.acc = self._train_words[:_lib.PPO_ACC["words"]]
-        self.ctl = self._train_words[_lib.PPO_ACC["words"]:].view(torch.int32)
-        self._idx, self._trains = None, {}
-        self._w2t = z(2 * 16 * 64)
+        self._init_train_state(clip_range_vf, target_kl)
+        self._w2t = self._zeros(2 * 16 * 64)
         self.refresh()
 
     def refresh(self):
@@ -144,15 +211,6 @@ class PPOLearner(_Learner):
         graph keeps the address).  ``update`` keeps both current itself."""
         self.seat.refresh()
         self._w2t.copy_(torch.from_numpy(pack_w2t(self._L, self.policy).reshape(-1)))
-
-    def set_clip_range_vf(self, clip_range_vf):
-        """Value clipping of the train sequence (``shuffle="device"``, ``train_graph``); None = off."""
-        self.hyper_ext[0] = float(clip_range_vf or 0.0)
-
-    def set_target_kl(self, target_kl):
-        """The train sequence's early stop: no epoch after one whose mean approx_kl exceeds
-        1.5 ``target_kl``; None = off."""
-        self.hyper_ext[1] = float(target_kl or 0.0)
 
     # ---- one minibatch ----
     def plan(self, B):
@@ -232,19 +290,7 @@ class PPOLearner(_Learner):
             for idx in self.minibatches(sink, batch_size or T * n, granule, generator):
                 self.update(sink, idx)
 
-    # ---- the train sequence: a whole train() on device-side state ----
-    def _train_state(self, sink):
-        tr = self._trains.get(id(sink))
-        if tr is None:
-            v = getattr(sink, "values", None)
-            if v is None or v.device != self.device or v.dtype != torch.float32 or not v.is_contiguous() \
-                    or v.shape != sink.advantages.shape:
-                raise ValueError("the sink's values: a contiguous float32 [T][n] tensor on %s" % (self.device,))
-            tr = _lib.PpoTrain(v.data_ptr(), self.hyper_ext.data_ptr(), self.ctl.data_ptr(), self.acc.data_ptr())
-            tr._keep = (v,)
-            self._trains[id(sink)] = tr
-        return tr
-
+    # ---- the train sequence: a whole train() on device-side state (the state and its readers: _Learner) ----
     def _sequence(self, sink, n_epochs, batch_size, granule, seed):
         """train_begin, then per epoch epoch_begin and one train_step per minibatch: a fixed, serial
         list of launches on the current stream -- no allocation after the first call for a sink's size,
@@ -256,11 +302,8 @@ class PPOLearner(_Learner):
             raise ValueError("batch_size must be positive")
         sizes = [min(bs, total - o) for o in range(0, total, bs)]
         cuts = [(o, b) for o, b in zip(range(0, total, bs), sizes) if b >= 2]
-        if self._idx is None or self._idx.numel() < total:
-            self._retired.append(self._idx)               # a captured graph may still write to it
-            self._idx = torch.zeros(total, dtype=torch.int32, device=self.device)
         self._check_outs(max(sizes))
-        idx, tr, L, dev = self._idx.data_ptr(), ctypes.byref(self._train_state(sink)), self._L, self._dev
+        idx, tr, L, dev = self._index_buffer(total).data_ptr(), ctypes.byref(self._train_state(sink)), self._L, self._dev
         seed = int(seed) & 0xFFFFFFFF
         _lib.call(L, "oc_policy_ppo_train_begin", dev, tr)
         for _ in range(n_epochs):
@@ -280,38 +323,12 @@ class PPOLearner(_Learner):
         ``replay()`` is one train(): the epoch counter lives on the device, so every replay shuffles anew,
         and ``set_lr`` / ``set_clip_range`` / ``set_clip_range_vf`` / ``set_target_kl`` act on the next replay."""
         granule = self._check_trainable(sink, granule)
-        with _lib.on_device(self._dev):
-            state = self._train_tensors()
-            saved = [t.clone() for t in state]
-            self._sequence(sink, 1, batch_size, granule, seed)        # (also sizes the index buffer and the scratch)
-            torch.cuda.synchronize(self.device)
-            with torch.no_grad():
-                for t, s in zip(state, saved):
-                    t.copy_(s)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._sequence(sink, int(n_epochs), batch_size, granule, seed)
-        return TrainGraph(self, sink, graph)
-
-    def train_stats(self):
-        """The reference's logged means over the updates APPLIED in the last train sequence -- policy_loss,
-        value_loss, entropy_loss, approx_kl, clip_fraction, loss -- with ``updates``, ``epochs`` (completed)
-        and ``stopped`` (by the KL rule).  ONE synchronisation, and only when called."""
-        host = self._train_words.cpu()
-        na = _lib.PPO_ACC["words"]
-        acc, ctl = host[:na].tolist(), host[na:].view(torch.int32).tolist()
-        if ctl[_lib.PPO_CTL["error"]]:
-            raise _lib.OcError("the train sequence halted: a permutation walk reached its cap (include/oc_policy.h)")
-        updates = ctl[_lib.PPO_CTL["updates"]]
-        out = {k: (acc[_lib.PPO_ACC["sums"] + i] / updates if updates else float("nan"))
-               for i, k in enumerate(TRAIN_STATS)}
-        out.update(updates=updates, stopped=bool(ctl[_lib.PPO_CTL["stop"]]),
-                   epochs=ctl[_lib.PPO_CTL["epochs"]] + (1 if acc[_lib.PPO_ACC["epoch_count"]] > 0 else 0))
-        return out
+        return self._capture(sink, lambda epochs: self._sequence(sink, int(epochs or n_epochs), batch_size, granule, seed))
 
 
 class TrainGraph:
-    """A captured train sequence (``PPOLearner.train_graph``): ``replay()`` is one train()."""
+    """A captured train sequence (``PPOLearner.train_graph``, ``RecurrentPPOLearner.train_graph``): ``replay()``
+    is one train()."""
 
     def __init__(self, learner, sink, graph):
         self.learner, self.sink, self.graph = learner, sink, graph
@@ -320,25 +337,44 @@ class TrainGraph:
         self.graph.replay()
 
 
+def env_cuts(n, T, envs_per_batch=None):
+    """The recurrent learner's minibatches as (offset, E) into a permutation of n envs: chunks of ``envs_per_batch``
+    envs in order (None: all of them), the last one shorter; one whose E T would be below 2 is dropped --
+    ``RecurrentPPOLearner.minibatches``' sizes."""
+    per = int(envs_per_batch or n)
+    if per < 1:
+        raise ValueError("envs_per_batch must be positive")
+    return [(o, min(per, n - o)) for o in range(0, n, per) if min(per, n - o) * T >= 2]
+
+
 class RecurrentPPOLearner(_Learner):
-    """The minibatch update of a ``FusedRecurrentPartner``'s ``LSTMActorCritic`` (include/oc_policy.h, last section:
+    """The minibatch update of a ``FusedRecurrentPartner``'s ``LSTMActorCritic`` (include/oc_policy.h:
     ``oc_policy_rppo_update``): advantage normalisation, the forward over whole recorded sequences from the
     seat's ``h0`` / ``c0`` (``seat.begin_rollout()``), the clipped loss, backpropagation through time, the norm
     clip, Adam and the repack of the seat's three images -- six launches on the device, in place, without a
     synchronisation, capturable.  A minibatch is a set of ENVS (int32 ``envs`` [E], repeats allowed): every env
     brings its whole sequence of T steps, B = E T.  The learner owns what ``PPOLearner`` owns, and ``_bwd``, the
     backward's image of Wh and [W2; wv] transposed.  ``lp_out`` / ``v_out`` (float32 [T][E], tests) receive the
-    forward.  Not here: windows shorter than the rollout, the train sequence on device-side state
-    (``shuffle="device"``, ``train_graph``, ``target_kl``, ``clip_range_vf``)."""
+    forward.
+
+    A whole ``train()`` can run on device-side state, as ``PPOLearner``'s does (``train(shuffle="device")``,
+    ``train_graph``; include/oc_policy.h, last section: ``oc_policy_recurrent_train_step``): the epoch's
+    permutation of the ENVS, stable-baselines3's ``clip_range_vf``, the ``target_kl`` stop and the logged means
+    (``train_stats``) then need neither a torch op nor a synchronisation, and the sequence is one graph.  The KL
+    rule is the reference's modular learner's, at the END of an epoch on the mean of ``approx_kl`` -- not
+    sb3_contrib ``RecurrentPPO``'s break in mid-epoch.  ``set_lr`` / ``set_clip_range`` / ``set_clip_range_vf`` /
+    ``set_target_kl`` are device writes: they act on the next replay.  Not here: windows shorter than the
+    rollout, the marginal-regularisation term."""
 
     def __init__(self, seat, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
-                 betas=(0.9, 0.999), eps=1e-5, max_groups=0):
+                 betas=(0.9, 0.999), eps=1e-5, max_groups=0, clip_range_vf=None, target_kl=None):
         if not isinstance(seat, FusedRecurrentPartner):
             raise TypeError("RecurrentPPOLearner updates a gym_comm_amd.vec_env.FusedRecurrentPartner")
         plan = (ctypes.c_int64 * 8)()
         _lib.check(seat._L.oc_policy_rppo_plan(seat.F, seat.C, 1, 2, 0, plan), "oc_policy_rppo_plan", seat._L)
         self._init_state(seat, RECURRENT_PARAMS, plan[3], lr, clip_range, ent_coef, vf_coef, max_grad_norm, betas, eps,
                          max_groups)
+        self._init_train_state(clip_range_vf, target_kl)
         self._bwd = self._zeros(self._L.oc_policy_rppo_pack_bwd_elems())
         self.refresh()
 
@@ -414,15 +450,73 @@ class RecurrentPPOLearner(_Learner):
         envs = (perm.unsqueeze(1) * g + torch.arange(g, device=self.device)).reshape(-1).to(torch.int32)
         return [b for b in envs.split(int(envs_per_batch)) if b.numel() * T >= 2]
 
-    def train(self, sink, n_epochs=10, envs_per_batch=None, granule=32, generator=None):
-        """``n_epochs`` passes over a FULL fused sink whose ``finish_rollout`` has run and whose slots are in
-        chronological order (``count == n_steps``, ``pos == 0``: ``seat.begin_rollout()``, then exactly
-        ``n_steps`` steps).  ``envs_per_batch=None``: every env in one minibatch."""
+    def _check_chronological(self, sink, granule):
+        """train()'s checks of the sink -- full, advantages ready, slots in chronological order (ONE
+        synchronisation: ``pos``); returns the granule to use."""
         granule = self._check_trainable(sink, granule)
         if sink.steps() != sink.n_steps or int(sink.pos.item()) != 0:
             raise ValueError("train() needs the sink's slots in chronological order: exactly %d steps since "
                              "begin_rollout() (count %d, pos %d)" % (sink.n_steps, sink.steps(), int(sink.pos.item())))
+        return granule
+
+    def train(self, sink, n_epochs=10, envs_per_batch=None, granule=32, generator=None, shuffle="torch", seed=0):
+        """``n_epochs`` passes over a FULL fused sink whose ``finish_rollout`` has run and whose slots are in
+        chronological order (``count == n_steps``, ``pos == 0``: ``seat.begin_rollout()``, then exactly
+        ``n_steps`` steps).  ``envs_per_batch=None``: every env in one minibatch.
+
+        ``shuffle="torch"``: ``minibatches`` (torch.randperm, ``generator``) and one ``update`` each.
+        ``shuffle="device"``: the train sequence of include/oc_policy.h, launched eagerly -- the permutation of
+        the envs from (``seed``, the learner's device-side epoch counter) written into the learner's own index
+        buffer, value clipping (``clip_range_vf``), the KL stop (``target_kl``) and the statistics
+        ``train_stats()`` reports all on the device; the same launches ``train_graph`` captures."""
+        if shuffle not in ("torch", "device"):
+            raise ValueError("shuffle: 'torch' or 'device' (got %r)" % (shuffle,))
+        granule = self._check_chronological(sink, granule)
+        if shuffle == "device":
+            return self._sequence(sink, int(n_epochs), envs_per_batch, granule, seed)
         n = sink.obs.shape[2]
         for _ in range(int(n_epochs)):
             for envs in self.minibatches(sink, envs_per_batch or n, granule, generator):
                 self.update(sink, envs)
+
+    # ---- the train sequence: a whole train() on device-side state (the state and its readers: _Learner) ----
+    def _sequence(self, sink, n_epochs, envs_per_batch, granule, seed):
+        """train_begin, then per epoch epoch_begin over the n envs and one recurrent train_step per cut of the
+        index buffer (``env_cuts``): a fixed, serial list of launches on the current stream.  The scratch is sized
+        once, for the largest cut, before the first launch; no allocation after the first call for a sink's
+        size, no synchronisation."""
+        T, _, n = sink.obs.shape
+        if self.seat.h0 is None:
+            raise ValueError("the seat holds no start state: call seat.begin_rollout() before the rollout")
+        cuts = env_cuts(n, T, envs_per_batch)
+        if not cuts:
+            raise ValueError("no minibatch of at least 2 samples (%d envs x %d steps)" % (n, T))
+        largest = max(E for _, E in cuts)
+        self._grow_scratch(self.plan(largest, T)[4])
+        self._check_outs(largest * T)
+        idx, tr, L, dev = self._index_buffer(n).data_ptr(), ctypes.byref(self._train_state(sink)), self._L, self._dev
+        cfg = ctypes.byref(self._cfg(sink, largest))
+        seed = int(seed) & 0xFFFFFFFF
+        _lib.call(L, "oc_policy_ppo_train_begin", dev, tr)
+        for _ in range(n_epochs):
+            _lib.call(L, "oc_policy_ppo_epoch_begin", dev, tr, idx, n, granule, seed)
+            for o, E in cuts:
+                _lib.call(L, "oc_policy_recurrent_train_step", dev, cfg, tr, idx + 4 * o, E)
+
+    def _train_tensors(self):
+        """Everything a train sequence writes that a later one reads (``seat.h0`` / ``c0`` are read only, and
+        ``begin_rollout()`` writes them in place: a captured graph's addresses stay good)."""
+        return list(self._params) + [self.m, self.v, self.step, self._bwd, self.stats_t, self.grad_flat,
+                                     self._train_words] + list(self.seat._w)
+
+    def train_graph(self, sink, n_epochs, envs_per_batch=None, granule=32, seed=0):
+        """``train(shuffle="device")`` captured into ONE graph: a strictly serial stream of launches.  ``train()``'s
+        host-side checks of the sink -- full, advantages ready, chronological order -- are made HERE, before the
+        capture, and synchronise once; a replay cannot make them: the caller must replay only on a full,
+        chronological, finished sink (``seat.begin_rollout()``, exactly ``n_steps`` steps, ``finish_rollout()``).
+        The sequence runs once eagerly first, the learner's state is put back, and the capture follows.  Returns a
+        ``TrainGraph`` whose ``replay()`` is one train(): the epoch counter lives on the device, so every replay
+        shuffles anew, and ``set_lr`` / ``set_clip_range`` / ``set_clip_range_vf`` / ``set_target_kl`` act on the
+        next replay."""
+        granule = self._check_chronological(sink, granule)
+        return self._capture(sink, lambda epochs: self._sequence(sink, int(epochs or n_epochs), envs_per_batch, granule, seed))

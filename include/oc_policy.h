@@ -330,7 +330,7 @@ OC_API int oc_policy_ppo_train_step(const oc_ppo_cfg *cfg, const oc_ppo_train *t
  * env (trainer.py:92-112: RecurrentPPO('MultiInputPolicy', ...), for the partner inside OnPolicyAgent) --
  * one LSTM cell of 64 units shared by actor and critic, its state kept per env and put back to zero
  * where an episode starts.  OUT OF SCOPE: hidden sizes other than 64, a separate critic LSTM.  (The update,
- * backpropagation through time: the last section of this header.)
+ * backpropagation through time: the section after this one.)
  *
  * The network (gym-comm_amd/partners.py: LSTMActorCritic), per env, H = 64, F observation rows x, gates
  * in torch.nn.LSTMCell's order i, f, g, o:
@@ -420,7 +420,6 @@ OC_API int oc_policy_lstm_ac(const oc_policy_lstm_player *pl, const double *time
  * clipped loss, the gradient through time, the norm clip, Adam, and the repack of the seat's three images in
  * place.  OUT OF SCOPE:
  *   - truncated windows shorter than the rollout, and states recorded mid-rollout
- *   - the train sequence (device shuffle, target_kl, clip_range_vf, train_graph) for the recurrent learner
  *   - the marginal-regularisation term
  *   - hidden sizes other than 64
  *   - a separate critic LSTM
@@ -525,6 +524,48 @@ OC_API int oc_policy_rppo_pack_bwd(const float *wh, const float *w2, const float
  * 1 <= C <= 16, T >= 1, E >= 1, 2 <= E T < 2^31, obs_type, T n < 2^31, 64 n < 2^31, non-NULL pointers. */
 OC_API int oc_policy_rppo_update(const oc_rppo_cfg *cfg, const int32_t *envs, int32_t E, void *stream);
 OC_API int oc_policy_rppo_grad(const oc_rppo_cfg *cfg, const int32_t *envs, int32_t E, void *stream);
+
+/* ---- the recurrent learner's train(): the train sequence over whole sequences -------------------------
+ *
+ * What it restates: the loops of train() around the minibatch of the section above -- the epoch's shuffle of the
+ * ENVS, the logged means, the early stop -- and clip_range_vf, exactly as the MLP seat's train sequence does
+ * (the section "a whole train() as a fixed sequence of launches on device-side state": the same oc_ppo_train
+ * state, the same halting rule, the same permutation).  The sequence is
+ *     oc_policy_ppo_train_begin,
+ *     n_epochs x ( oc_policy_ppo_epoch_begin(train, idx, count = n, granule, seed),
+ *                  oc_policy_recurrent_train_step per cut of idx )
+ * whose first two calls are unchanged: with count = n and a granule dividing n they write a permutation of the
+ * sink's envs into idx, int32 [n], and a cut of E consecutive elements of idx (E >= 1, E T >= 2) is a minibatch
+ * of E whole sequences.  The same serial list of launches whatever happens in it; it never allocates or
+ * synchronises and can be captured into ONE graph.
+ *
+ * The KL rule is the sequence's own, the reference's modular learner (learn.py:328-332): at the END of an epoch,
+ * applied by the next oc_policy_ppo_epoch_begin to the mean over that epoch's minibatches of approx_kl =
+ * mean(old_lp - lp); where it exceeds 1.5 target_kl no further epoch runs.  It is NOT sb3_contrib RecurrentPPO's
+ * rule, which breaks in mid-epoch, before the minibatch that crosses the line is applied, on the estimator
+ * mean((rho - 1) - log rho) (ppo_recurrent.py:407-412).  OUT OF SCOPE: sb3_contrib's mid-epoch break and its
+ * estimator; truncated windows shorter than the rollout; the marginal-regularisation term.
+ *
+ * Value clipping, where c = hyper_ext[0] = clip_range_vf > 0: with old_v = values[t * n + env] the recorded value
+ * of sample (t, env), in float32,
+ *     v_pred = old_v + clamp(v - old_v, -c, c)
+ *     value_loss = mean((ret - v_pred)^2)
+ *     the value head's row of D_t = 2 vf_coef (v_pred - ret)  where -c <= v - old_v <= c (the ends included),
+ *                                   0 elsewhere
+ * and everything behind D_t is the section above's: the gradient through time is linear in D.  A bad-action
+ * sample stays excluded.  Where c <= 0 or c is NaN every output is bit for bit oc_policy_rppo_update's.
+ *
+ * oc_policy_recurrent_train_step: oc_policy_rppo_update's six launches (the TRAIN variants of its kernels, a
+ * code object of their own) and all of its argument checks, and the train state's non-NULL pointers; everything
+ * is checked before any device work.  After cfg.stats is written, the one thread that wrote it adds the six
+ * float statistics, converted to double, to acc[OC_PPO_ACC_SUMS + k], adds approx_kl to acc[OC_PPO_ACC_EPOCH_KL]
+ * and 1 to acc[OC_PPO_ACC_EPOCH_COUNT], and bumps ctl[OC_PPO_CTL_UPDATES]: no atomics, and the same sequence
+ * gives the same bits.  HALTED (ctl[OC_PPO_CTL_STOP] or ctl[OC_PPO_CTL_ERROR] non-zero): each of the six
+ * launches returns at once, having written nothing -- not the parameters, m, v, step, the three images, bwd,
+ * grad, scratch, stats (stats[6], [7] included), the sums or lp_out / v_out.  Never allocates or synchronises;
+ * capturable. */
+OC_API int oc_policy_recurrent_train_step(const oc_rppo_cfg *cfg, const oc_ppo_train *train, const int32_t *envs,
+                                          int32_t E, void *stream);
 
 #ifdef __cplusplus
 }
