@@ -5,10 +5,14 @@ hipGraph per 16 steps; then GAE in one launch and the PPO update over whole reco
 backpropagation through time, clip, Adam and the repack of the seat's weights -- in six launches per minibatch
 (`RecurrentPPOLearner`, include/oc_policy.h: `oc_policy_rppo_update`).  With `--graph` the whole train() -- the
 epochs' shuffles of the envs, the minibatches, the KL stop, value clipping, the logged means -- is ONE captured
-graph (`train_graph`, `oc_policy_recurrent_train_step`), replayed once per round.
+graph (`train_graph`, `oc_policy_recurrent_train_step`), replayed once per round.  With `--window W` the seat records
+its state every W steps (`RolloutSink(state_window=W)`, `oc_policy_window_snapshot`) and a minibatch is a set of
+WINDOWS of W steps, each unrolled from its recorded state (`train_windows`, `oc_policy_window_gather`): truncated
+backpropagation through time.
 
     python examples/train_recurrent_ppo.py --envs 4096 --rounds 4
     python examples/train_recurrent_ppo.py --envs 4096 --rounds 4 --graph --target-kl 0.03 --clip-range-vf 0.2
+    python examples/train_recurrent_ppo.py --envs 4096 --rounds 4 --graph --window 16 --sequences-per-batch 8192
 """
 import argparse
 import os
@@ -31,18 +35,24 @@ def main():
     p.add_argument("--n-steps", type=int, default=128)
     p.add_argument("--epochs", type=int, default=4)
     p.add_argument("--envs-per-batch", type=int, default=1024)
+    p.add_argument("--window", type=int, default=None, help="train on windows of this many steps (it divides --n-steps)")
+    p.add_argument("--sequences-per-batch", type=int, default=None,
+                   help="with --window: windows per minibatch (default: --envs-per-batch x n-steps / window, the same samples)")
     p.add_argument("--graph", action="store_true", help="replay one captured train_graph per round; print train_stats()")
     p.add_argument("--target-kl", type=float, default=None, help="no epoch after one whose mean approx_kl exceeds 1.5 x this")
     p.add_argument("--clip-range-vf", type=float, default=None, help="value clipping around the recorded value")
     a = p.parse_args()
     if a.n_steps % 16:
         p.error("--n-steps is a multiple of 16 (the closed loop replays 16 steps at a time)")
+    if a.window is not None and (a.window < 1 or a.n_steps % a.window):
+        p.error("--window divides --n-steps")
+    per = a.sequences_per_batch or (a.envs_per_batch * a.n_steps // a.window if a.window else None)
     C = 2
     cfg = load_env_args({"level": a.level, "num_agents": 2, "max_num_timesteps": 100,
                          "communication_on": True, "num_communication": C, "fow_radius": 2})
     venv = OvercookedVecEnv(cfg, a.envs, obs_dtype=torch.float32)
     pol = LSTMActorCritic(venv._b.S, C, seed=1).cuda()
-    sink = RolloutSink(a.n_steps, a.envs, venv._b.F, obs_dtype=torch.float32, fused=True)
+    sink = RolloutSink(a.n_steps, a.envs, venv._b.F, obs_dtype=torch.float32, fused=True, state_window=a.window)
     venv.partner = seat = FusedRecurrentPartner(pol, sample=True, seed=7, sink=sink)
     learner = RecurrentPPOLearner(seat, lr=3e-4, ent_coef=0.01, clip_range_vf=a.clip_range_vf, target_kl=a.target_kl)
     device = a.graph or a.target_kl is not None or a.clip_range_vf is not None    # both live in the train sequence
@@ -58,8 +68,12 @@ def main():
         seat.finish_rollout(gamma=0.99, gae_lambda=0.95)
         if a.graph:
             if graph is None:                        # the first full, finished sink: checked here, captured once
-                graph = learner.train_graph(sink, a.epochs, envs_per_batch=a.envs_per_batch, seed=r)
+                graph = (learner.train_graph_windows(sink, a.epochs, sequences_per_batch=per, seed=r) if a.window else
+                         learner.train_graph(sink, a.epochs, envs_per_batch=a.envs_per_batch, seed=r))
             graph.replay()
+        elif a.window:
+            learner.train_windows(sink, n_epochs=a.epochs, sequences_per_batch=per, shuffle="device" if device else "torch",
+                                  seed=r)
         else:
             learner.train(sink, n_epochs=a.epochs, envs_per_batch=a.envs_per_batch, shuffle="device" if device else "torch",
                           seed=r)

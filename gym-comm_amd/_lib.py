@@ -87,6 +87,22 @@ class RppoCfg(ctypes.Structure):
                [("max_groups", ctypes.c_int32), ("lp_out", ctypes.c_void_p), ("v_out", ctypes.c_void_p)]
 
 
+class WindowSrc(ctypes.Structure):
+    """oc_window_src (include/oc_policy.h): a sink's tensors and the states recorded where its windows begin."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "timestep", "actions", "log_probs", "advantages", "returns", "episode_starts", "values",
+                 "states")] + \
+               [("n", ctypes.c_int64), ("T", ctypes.c_int32), ("W", ctypes.c_int32), ("F", ctypes.c_int32),
+                ("obs_type", ctypes.c_int32)]
+
+
+class WindowBatch(ctypes.Structure):
+    """oc_window_batch (include/oc_policy.h): a minibatch of windows laid out as a sink of W slots and E envs."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "timestep", "actions", "log_probs", "advantages", "returns", "episode_starts", "values",
+                 "h0", "c0")]
+
+
 class PpoTrain(ctypes.Structure):
     """oc_ppo_train (include/oc_policy.h): the train sequence's device state."""
     _fields_ = [(name, ctypes.c_void_p) for name in ("values", "hyper_ext", "ctl", "acc")]
@@ -181,6 +197,9 @@ def _libs_table():
             "oc_policy_lstm_pack_head": (cint, [fp, fp, i32, vp]),
             "oc_policy_lstm_pack_head_bias": (cint, [fp, fp, i32, fp]),
             "oc_policy_lstm_ac": (cint, [P(PolicyLstmPlayer), vp, i32, i32, i32, i64, vp]),
+            # windows of a rollout: the state snapshot and the gather of a minibatch of windows
+            "oc_policy_window_snapshot": (cint, [vp, i32, i32, vp, vp, vp, i64, vp]),
+            "oc_policy_window_gather": (cint, [P(WindowSrc), P(WindowBatch), vp, i32, vp]),
             # the recurrent seat's PPO update
             "oc_policy_rppo_plan": (cint, [i32, i32, i32, i32, i32, P(i64)]),
             "oc_policy_rppo_pack_bwd_elems": (i32, None),

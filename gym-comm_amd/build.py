@@ -34,11 +34,11 @@ LIBS = {
     # the policy library (include/oc_policy.h): its own translation unit and shared object, so that
     # the stepper's specialised builds neither contain nor depend on it
     # (oc_policy_ppo.hip: the PPO update, a second translation unit and code object of the same library;
-    # oc_policy_lstm.hip: the recurrent seat, a third; oc_policy_rppo.hip: the recurrent update, a fourth;
-    # oc_policy_rtrain.hip: the recurrent learner's step of the train sequence, a fifth;
+    # oc_policy_lstm.hip: the recurrent seat, a third; oc_policy_window.hip: the window snapshot and gather;
+    # oc_policy_rppo.hip: the recurrent update; oc_policy_rtrain.hip: the recurrent learner's step of the train sequence;
     # oc_policy_train.hip: the train sequence, kept LAST: the code objects keep their order)
-    "policy": Lib(["oc_policy.hip", "oc_policy_ppo.hip", "oc_policy_lstm.hip", "oc_policy_rppo.hip", "oc_policy_rtrain.hip",
-                   "oc_policy_train.hip"],
+    "policy": Lib(["oc_policy.hip", "oc_policy_ppo.hip", "oc_policy_lstm.hip", "oc_policy_window.hip", "oc_policy_rppo.hip",
+                   "oc_policy_rtrain.hip", "oc_policy_train.hip"],
                   ["oc_policy.h"],
                   ["oc_policy_device.h", "oc_policy_ac_device.h", "oc_policy_ppo_device.h", "oc_policy_layout.h",
                    "oc_policy_fail.h", "oc_policy_shuffle.h", "oc_policy_rppo_device.h", "oc_policy_rppo_host.h"],

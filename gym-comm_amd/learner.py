@@ -2,7 +2,9 @@
 launches per minibatch (include/oc_policy.h: ``oc_policy_ppo_update``); ``RecurrentPPOLearner``: the update of a
 ``FusedRecurrentPartner``'s ``LSTMActorCritic`` over whole recorded sequences, six launches per minibatch
 (``oc_policy_rppo_update``).  Both run a whole ``train()`` on device-side state as well (``shuffle="device"``,
-``train_graph``: the train sequence of include/oc_policy.h) -- see ``vec_env`` for the overview."""
+``train_graph``: the train sequence of include/oc_policy.h), and the recurrent learner trains on WINDOWS of a rollout too,
+from the states its seat recorded mid-rollout (``update_windows``, ``train_windows``, ``train_graph_windows``:
+``oc_policy_window_gather`` in front of the same update) -- see ``vec_env`` for the overview."""
 import ctypes
 
 import torch
@@ -347,6 +349,58 @@ def env_cuts(n, T, envs_per_batch=None):
     return [(o, min(per, n - o)) for o in range(0, n, per) if min(per, n - o) * T >= 2]
 
 
+def sequence_ids(n, T, W):
+    """The ids of a rollout's windows as (window, env) -- include/oc_policy.h, "windows of a rollout": sequence
+    s = k n + env is window k (slots k W .. k W + W - 1) of env ``env``; returns two int64 CPU tensors [n T / W]."""
+    n, T, W = int(n), int(T), int(W)
+    if W < 1 or T % W:
+        raise ValueError("window %d does not divide the rollout's %d steps" % (W, T))
+    s = torch.arange(n * (T // W))
+    return s // n, s % n
+
+
+def sequence_cuts(count, W, sequences_per_batch=None):
+    """The windowed train()'s minibatches as (offset, E) into a permutation of ``count`` sequence ids: ``env_cuts``
+    with a window's W steps per sequence."""
+    return env_cuts(count, W, sequences_per_batch)
+
+
+class _WindowBatch:
+    """The learner's staging for a minibatch of windows (include/oc_policy.h: oc_window_batch): flat storage for up
+    to ``cap`` sequences of W steps, which a minibatch of E <= cap sequences uses from its start, laid out as a sink
+    of W slots and E envs; the start states ``h0`` / ``c0`` ([64][E]) and the constant ``envs`` = 0 .. cap - 1 whose
+    first E elements the update is handed."""
+    FLOATS = ("log_probs", "advantages", "returns", "episode_starts", "values")
+
+    def __init__(self, W, F, cap, obs_dtype, device):
+        z = lambda count, dt: torch.zeros(count, dtype=dt, device=device)  # noqa: E731
+        self.W, self.F, self.cap, self.obs_dtype = W, F, cap, obs_dtype
+        self.obs = z(W * F * cap, obs_dtype)
+        self.timestep = z(W * cap, torch.float64)
+        self.actions = z(W * 2 * cap, torch.int32)
+        for name in self.FLOATS:
+            setattr(self, name, z(W * cap, torch.float32))
+        self.h0, self.c0 = z(64 * cap, torch.float32), z(64 * cap, torch.float32)
+        self.envs = torch.arange(cap, dtype=torch.int32, device=device)
+        self.c_struct = _lib.WindowBatch(*[t.data_ptr() for t in self.tensors()])
+
+    def tensors(self):
+        """The ten tensors in oc_window_batch's order."""
+        return [self.obs, self.timestep, self.actions] + [getattr(self, k) for k in self.FLOATS] + [self.h0, self.c0]
+
+    def fits(self, W, F, E, obs_dtype):
+        return (self.W, self.F, self.obs_dtype) == (W, F, obs_dtype) and E <= self.cap
+
+    def view(self, name, E):
+        """Tensor ``name`` as a minibatch of E sequences sees it: [W][F][E], [W][2][E], [W][E] or [64][E]."""
+        W, F = self.W, self.F
+        shape = {"obs": (W, F, E), "actions": (W, 2, E), "h0": (64, E), "c0": (64, E)}.get(name, (W, E))
+        count = 1
+        for d in shape:
+            count *= d
+        return getattr(self, name)[:count].view(shape)
+
+
 class RecurrentPPOLearner(_Learner):
     """The minibatch update of a ``FusedRecurrentPartner``'s ``LSTMActorCritic`` (include/oc_policy.h:
     ``oc_policy_rppo_update``): advantage normalisation, the forward over whole recorded sequences from the
@@ -363,8 +417,16 @@ class RecurrentPPOLearner(_Learner):
     (``train_stats``) then need neither a torch op nor a synchronisation, and the sequence is one graph.  The KL
     rule is the reference's modular learner's, at the END of an epoch on the mean of ``approx_kl`` -- not
     sb3_contrib ``RecurrentPPO``'s break in mid-epoch.  ``set_lr`` / ``set_clip_range`` / ``set_clip_range_vf`` /
-    ``set_target_kl`` are device writes: they act on the next replay.  Not here: windows shorter than the
-    rollout, the marginal-regularisation term."""
+    ``set_target_kl`` are device writes: they act on the next replay.
+
+    Windows (include/oc_policy.h, "windows of a rollout").  On a ``RolloutSink(..., state_window=W)`` whose seat
+    recorded its state where every window begins, a minibatch can be a set of WINDOWS of W steps instead: int32
+    ``seqs`` [E] of sequence ids (``sequence_ids``), each unrolled from its recorded state, which is a constant in
+    the gradient (truncated backpropagation through time).  ``update_windows`` / ``grad_windows`` gather the
+    minibatch into the learner's own window batch (one launch) and run the unchanged update on it as on a sink of
+    W slots and E envs: seven launches.  ``train_windows`` / ``train_graph_windows`` are ``train`` / ``train_graph``
+    over sequence ids.  Not here: windows that do not divide the rollout, a state recorded at every step,
+    sb3_contrib's exact contiguous-chunk minibatches, the marginal-regularisation term."""
 
     def __init__(self, seat, lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  betas=(0.9, 0.999), eps=1e-5, max_groups=0, clip_range_vf=None, target_kl=None):
@@ -376,6 +438,7 @@ class RecurrentPPOLearner(_Learner):
                          max_groups)
         self._init_train_state(clip_range_vf, target_kl)
         self._bwd = self._zeros(self._L.oc_policy_rppo_pack_bwd_elems())
+        self._wbatch, self._wsrcs = None, {}          # the window batch (allocated by the first windowed call)
         self.refresh()
 
     def refresh(self):
@@ -392,6 +455,18 @@ class RecurrentPPOLearner(_Learner):
                    "oc_policy_rppo_plan", self._L)
         return tuple(int(v) for v in plan)
 
+    def _build_cfg(self, rollout_ptrs, h0, c0, n, T, obs_type):
+        """An oc_rppo_cfg over the seven rollout tensors at ``rollout_ptrs`` and the start state (h0, c0)."""
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        return _lib.RppoCfg(
+            *rollout_ptrs, h0.data_ptr(), c0.data_ptr(), n, T, self.F, self.C,
+            obs_type, *self.seat.weight_ptrs(), self._bwd.data_ptr(),
+            *[t.data_ptr() for t in self._params],
+            self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.grad_flat.data_ptr(),
+            self._scratch.data_ptr(), self.stats_t.data_ptr(), self.hyper.data_ptr(),
+            self.ent_coef, self.vf_coef, self.max_grad_norm, self.betas[0], self.betas[1], self.eps,
+            self.max_groups, ptr(self.lp_out), ptr(self.v_out))
+
     def _cfg(self, sink, E):
         T = sink.obs.shape[0]
         self._grow_scratch(self.plan(E, T)[4])
@@ -404,15 +479,7 @@ class RecurrentPPOLearner(_Learner):
                                                    "episode_starts"))
             if seat.h0 is None or tuple(seat.h0.shape) != (64, n):
                 raise ValueError("the seat holds no start state for %d envs: call seat.begin_rollout() before the rollout" % n)
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            cfg = _lib.RppoCfg(
-                *[t.data_ptr() for t in keep], seat.h0.data_ptr(), seat.c0.data_ptr(), n, T, self.F, self.C,
-                OBS_TYPE[sink.obs.dtype], *seat.weight_ptrs(), self._bwd.data_ptr(),
-                *[t.data_ptr() for t in self._params],
-                self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), self.grad_flat.data_ptr(),
-                self._scratch.data_ptr(), self.stats_t.data_ptr(), self.hyper.data_ptr(),
-                self.ent_coef, self.vf_coef, self.max_grad_norm, self.betas[0], self.betas[1], self.eps,
-                self.max_groups, ptr(self.lp_out), ptr(self.v_out))
+            cfg = self._build_cfg([t.data_ptr() for t in keep], seat.h0, seat.c0, n, T, OBS_TYPE[sink.obs.dtype])
             cfg._keep = keep + (seat.h0, seat.c0)
             self._cfgs[key] = cfg
         return cfg
@@ -520,3 +587,144 @@ class RecurrentPPOLearner(_Learner):
         next replay."""
         granule = self._check_chronological(sink, granule)
         return self._capture(sink, lambda epochs: self._sequence(sink, int(epochs or n_epochs), envs_per_batch, granule, seed))
+
+    # ---- windows: minibatches of W-step stretches from the states the seat recorded mid-rollout ----
+    def sequences(self, sink):
+        """How many windows the sink's rollout holds: ``n * n_steps // state_window``."""
+        W = self._window(sink)
+        T, _, n = sink.obs.shape
+        return n * T // W
+
+    @staticmethod
+    def _window(sink):
+        W = getattr(sink, "state_window", None)
+        if W is None:
+            raise ValueError("windows need a RolloutSink(..., state_window=W) whose seat recorded its states")
+        return int(W)
+
+    def _window_src(self, sink):
+        """The sink as the gather reads it (oc_window_src), checked once per sink."""
+        src = self._wsrcs.get(id(sink))
+        if src is None:
+            W = self._window(sink)
+            keep, T, n = self._sink_tensors(sink, ("obs", "timestep", "actions", "log_probs", "advantages", "returns",
+                                                   "episode_starts", "values", "lstm_states"))
+            if tuple(sink.lstm_states.shape) != (T // W, 2, 64, n) or sink.lstm_states.dtype != torch.float32:
+                raise ValueError("the sink's lstm_states: float32 [%d][2][64][%d]" % (T // W, n))
+            src = _lib.WindowSrc(*[t.data_ptr() for t in keep], n, T, W, self.F, OBS_TYPE[sink.obs.dtype])
+            src._keep = keep
+            self._wsrcs[id(sink)] = src
+        return src
+
+    def _window_batch(self, sink, E):
+        """The learner's own window batch with room for E sequences of the sink's windows; regrows by retiring, as
+        the scratch and the index buffer do (a captured graph may still write to the old one)."""
+        W, b = self._window(sink), self._wbatch
+        if b is None or not b.fits(W, self.F, E, sink.obs.dtype):
+            self._retired.append(b)
+            b = self._wbatch = _WindowBatch(W, self.F, max(E, b.cap if b is not None else 0), sink.obs.dtype, self.device)
+        return b
+
+    def _batch_cfg(self, batch, E):
+        """The cfg that shows the update E gathered sequences as a full sink of W slots and E envs."""
+        self._grow_scratch(self.plan(E, batch.W)[4])
+        key = (id(batch), E, self.max_groups, None if self.lp_out is None else self.lp_out.data_ptr(),
+               None if self.v_out is None else self.v_out.data_ptr())
+        cfg = self._cfgs.get(key)
+        if cfg is None:
+            keep = batch.tensors()
+            cfg = self._build_cfg([t.data_ptr() for t in keep[:3]] + [getattr(batch, k).data_ptr() for k in
+                                  ("log_probs", "advantages", "returns", "episode_starts")],
+                                  batch.h0, batch.c0, E, batch.W, OBS_TYPE[batch.obs_dtype])
+            cfg._keep = tuple(keep)
+            self._cfgs[key] = cfg
+        return cfg
+
+    def _gather(self, sink, batch, seqs_ptr, E):
+        _lib.call(self._L, "oc_policy_window_gather", self._dev, ctypes.byref(self._window_src(sink)),
+                  ctypes.byref(batch.c_struct), seqs_ptr, E)
+
+    def _run_windows(self, name, sink, seqs):
+        if seqs.dtype != torch.int32 or seqs.dim() != 1 or not seqs.is_contiguous() or seqs.device != self.device:
+            raise ValueError("seqs: a contiguous int32 [E] tensor on %s" % (self.device,))
+        E = seqs.numel()
+        batch = self._window_batch(sink, E)
+        self._check_outs(E * batch.W)
+        self._gather(sink, batch, seqs.data_ptr(), E)
+        _lib.call(self._L, name, self._dev, ctypes.byref(self._batch_cfg(batch, E)), batch.envs.data_ptr(), E)
+
+    def update_windows(self, sink, seqs):
+        """One minibatch of WINDOWS: int32 ``seqs`` [E] of sequence ids (``sequence_ids``; any order, repeats
+        allowed), each window unrolled from the state recorded where it begins.  One gather into the learner's
+        window batch, then ``update``'s six launches on it: seven launches, no synchronisation.  ``lp_out`` /
+        ``v_out`` receive float [W][E].  The sink must be full and chronological (``train_windows`` checks it)."""
+        self._run_windows("oc_policy_rppo_update", sink, seqs)
+
+    def grad_windows(self, sink, seqs):
+        """The clipped gradient and the statistics of a minibatch of windows only (``grad``'s counterpart)."""
+        self._run_windows("oc_policy_rppo_grad", sink, seqs)
+        return self.grads
+
+    def minibatches_windows(self, sink, sequences_per_batch, granule=32, generator=None):
+        """A device permutation (``torch.randperm``) of the sink's sequence ids, cut into int32 tensors of
+        ``sequences_per_batch``; ``granule`` must divide the envs, so that a tile of ``granule`` ids stays inside one
+        window and its rows load coalesced."""
+        W, count = self._window(sink), self.sequences(sink)
+        n, g = sink.obs.shape[2], int(granule)
+        if g < 1 or n % g:
+            raise ValueError("granule %d does not divide the sink's %d envs" % (g, n))
+        perm = torch.randperm(count // g, device=self.device, generator=generator)
+        seqs = (perm.unsqueeze(1) * g + torch.arange(g, device=self.device)).reshape(-1).to(torch.int32)
+        return [b for b in seqs.split(int(sequences_per_batch)) if b.numel() * W >= 2]
+
+    def train_windows(self, sink, n_epochs=10, sequences_per_batch=None, granule=32, generator=None, shuffle="torch",
+                      seed=0):
+        """``train`` over WINDOWS of ``sink.state_window`` steps: the same checks of the sink, the same two shuffles,
+        the same train sequence -- over the n T / W sequence ids instead of the n envs, with one gather in front of
+        every minibatch.  ``sequences_per_batch=None``: every window in one minibatch.  With ``shuffle="device"``,
+        ``clip_range_vf`` clips about the recorded values of the gathered samples, and the KL rule, ``train_stats()``
+        and the setters are ``train``'s."""
+        if shuffle not in ("torch", "device"):
+            raise ValueError("shuffle: 'torch' or 'device' (got %r)" % (shuffle,))
+        self._window(sink)
+        granule = self._check_chronological(sink, granule)
+        if shuffle == "device":
+            return self._sequence_windows(sink, int(n_epochs), sequences_per_batch, granule, seed)
+        for _ in range(int(n_epochs)):
+            for seqs in self.minibatches_windows(sink, sequences_per_batch or self.sequences(sink), granule, generator):
+                self.update_windows(sink, seqs)
+
+    def _sequence_windows(self, sink, n_epochs, sequences_per_batch, granule, seed):
+        """``_sequence`` over sequence ids: epoch_begin with count = n T / W, and per cut of the index buffer one
+        gather and one recurrent train_step on the window batch.  The gather is not held back by a halted sequence:
+        it writes the learner's staging only."""
+        W, count = self._window(sink), self.sequences(sink)
+        cuts = sequence_cuts(count, W, sequences_per_batch)
+        if not cuts:
+            raise ValueError("no minibatch of at least 2 samples (%d windows of %d steps)" % (count, W))
+        largest = max(E for _, E in cuts)
+        self._grow_scratch(self.plan(largest, W)[4])
+        self._check_outs(largest * W)
+        batch = self._window_batch(sink, largest)
+        tr = self._trains.get(id(batch))
+        if tr is None:
+            tr = self._trains[id(batch)] = _lib.PpoTrain(batch.values.data_ptr(), self.hyper_ext.data_ptr(),
+                                                         self.ctl.data_ptr(), self.acc.data_ptr())
+            tr._keep = (batch,)
+        idx, L, dev = self._index_buffer(count).data_ptr(), self._L, self._dev
+        cfgs = {E: ctypes.byref(self._batch_cfg(batch, E)) for E in sorted({E for _, E in cuts}, reverse=True)}
+        envs, seed = batch.envs.data_ptr(), int(seed) & 0xFFFFFFFF
+        _lib.call(L, "oc_policy_ppo_train_begin", dev, ctypes.byref(tr))
+        for _ in range(n_epochs):
+            _lib.call(L, "oc_policy_ppo_epoch_begin", dev, ctypes.byref(tr), idx, count, granule, seed)
+            for o, E in cuts:
+                self._gather(sink, batch, idx + 4 * o, E)
+                _lib.call(L, "oc_policy_recurrent_train_step", dev, cfgs[E], ctypes.byref(tr), envs, E)
+
+    def train_graph_windows(self, sink, n_epochs, sequences_per_batch=None, granule=32, seed=0):
+        """``train_windows(shuffle="device")`` captured into ONE graph, as ``train_graph`` captures ``train``: the
+        checks of the sink are made here, before the capture; every replay shuffles anew."""
+        self._window(sink)
+        granule = self._check_chronological(sink, granule)
+        return self._capture(sink, lambda epochs: self._sequence_windows(sink, int(epochs or n_epochs),
+                                                                         sequences_per_batch, granule, seed))

@@ -663,7 +663,9 @@ class FusedRecurrentPartner(_RecordingSeat):
     ``score(obs, state, episode_start, pairs)`` evaluates GIVEN actions from a GIVEN state and writes no
     state at all.  ``begin_rollout()`` (called where ``sink.reset()`` is called otherwise) keeps the state the
     rollout starts from in ``h0`` / ``c0``: what ``RecurrentPPOLearner`` (learner.py) unrolls the recorded
-    sequences from."""
+    sequences from.  With a sink that has a ``state_window`` W the seat also records ``h`` / ``c`` in front of every
+    W-th step into ``sink.lstm_states`` (``oc_policy_window_snapshot``, one launch more per step): what the learner
+    unrolls WINDOWS of W steps from."""
     graph_safe = True
 
     def __init__(self, policy, sample=True, seed=None, device="cuda", sink=None, keep_logits=False):
@@ -737,12 +739,20 @@ class FusedRecurrentPartner(_RecordingSeat):
 
     def act_into(self, obs, move_row, comm_row):
         """ONE launch: the actions into ``move_row`` / ``comm_row`` (the env's own rows, no copy),
-        ``self.log_prob``, ``self.value`` and the new ``self.h`` / ``self.c``; then the sink's ``add``."""
+        ``self.log_prob``, ``self.value`` and the new ``self.h`` / ``self.c``; then the sink's ``add``.  A sink with a
+        ``state_window`` gets one launch more, in front: the snapshot of ``h`` / ``c`` into its ``lstm_states``."""
         rows, ts = rows_and_timestep(obs)
         n = rows.shape[1]
         self._buffers(n)
         row = FusedActorCriticPartner._action_row
         state = (self.h, self.c)
+        sink = self.sink
+        if sink is not None and getattr(sink, "state_window", None) is not None:
+            # the state BEFORE this step, kept where a window begins (one launch; it copies on every W-th slot only)
+            if tuple(sink.lstm_states.shape[2:]) != (64, n):
+                raise ValueError("the sink records states of %d envs, the seat steps %d" % (sink.lstm_states.shape[3], n))
+            _lib.call(self._L, "oc_policy_window_snapshot", rows.device.index, sink.pos.data_ptr(), sink.n_steps,
+                      sink.state_window, self.h.data_ptr(), self.c.data_ptr(), sink.lstm_states.data_ptr(), n)
         self._launch(rows, ts, state, state, self.episode_start, None, row(move_row, n), row(comm_row, n),
                      self.log_prob, self.value)
         if self.sink is not None:

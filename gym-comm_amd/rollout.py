@@ -21,11 +21,25 @@ class RolloutSink:
     ``fused=True``: the same tensors and counters, written by ``liboc_rollout.so``
     (include/oc_rollout.h) -- ONE launch per ``add``, one per ``add_reward`` (about a dozen and four
     torch launches otherwise), storing the same bits -- plus ``advantages`` / ``returns`` filled by
-    ONE launch of ``compute_returns_and_advantage`` (the third buffer call of agents.py:127-131)."""
+    ONE launch of ``compute_returns_and_advantage`` (the third buffer call of agents.py:127-131).
 
-    def __init__(self, n_steps, n, rows, device="cuda", obs_dtype=torch.int32, fused=False):
+    ``state_window=W`` (a fused sink only, W dividing ``n_steps``): the sink also holds ``lstm_states``, float32
+    ``[n_steps / W][2][64][n]`` -- room for a recurrent seat's (h, c) before the step of every W-th slot, which a
+    ``FusedRecurrentPartner`` records there (include/oc_policy.h: ``oc_policy_window_snapshot``) and from which
+    ``RecurrentPPOLearner`` unrolls windows of W steps.  ``None``: no such tensor, nothing changes."""
+
+    def __init__(self, n_steps, n, rows, device="cuda", obs_dtype=torch.int32, fused=False, state_window=None):
         dev = torch.device(device)
         T = self.n_steps = int(n_steps)
+        self.state_window = self.lstm_states = None
+        if state_window is not None:
+            W = int(state_window)
+            if not fused:
+                raise ValueError("state_window needs a RolloutSink(fused=True): the snapshot kernel reads the sink's "
+                                 "position as a device word")
+            if W < 1 or T % W:
+                raise ValueError("state_window %d does not divide the sink's %d steps" % (W, T))
+            self.state_window = W
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         self.obs = z((T, int(rows), n), obs_dtype)       # the viewer's [F][n] rows as they lie
         self.timestep = z((T, n), torch.float64)
@@ -57,6 +71,8 @@ class RolloutSink:
                                          self.episode_starts, self.rewards, self.dones, self.pos, self.last,
                                          self.count, self.ticket, self.advantages, self.returns)],
                 n, T, int(rows), OBS_TYPE[obs_dtype])
+            if self.state_window is not None:
+                self.lstm_states = z((T // self.state_window, 2, 64, n), torch.float32)
 
     def _call(self, name, *args):
         """One entry point of liboc_rollout.so on the current torch stream of the sink's device."""
@@ -166,9 +182,12 @@ class RolloutSink:
             self.ticket.zero_()
 
     def get_state(self):
-        return self.pos.clone(), self.last.clone(), self.count.clone()
+        st = self.pos.clone(), self.last.clone(), self.count.clone()
+        return st if self.lstm_states is None else st + (self.lstm_states.clone(),)
 
     def set_state(self, st):
         self.pos.copy_(st[0])
         self.last.copy_(st[1])
         self.count.copy_(st[2])
+        if self.lstm_states is not None:
+            self.lstm_states.copy_(st[3])

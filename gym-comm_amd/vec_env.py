@@ -37,7 +37,9 @@ Partners
                            the repack of the seat's weights in three launches per minibatch;
   ``FusedRecurrentPartner``  an ``LSTMActorCritic`` in the seat of a recurrent player, one launch per step;
                            ``RecurrentPPOLearner`` (learner.py) is its update over whole recorded sequences:
-                           forward, backpropagation through time, clip, Adam and the repack in six launches;
+                           forward, backpropagation through time, clip, Adam and the repack in six launches,
+                           or over windows of the rollout from the states the seat recorded every W steps
+                           (``RolloutSink(state_window=W)``, ``train_windows``): one gather launch more;
   any callable ``partner(obs_dict) -> [n, 2]`` still works (slow path).
 How a seated player yields its actions -- pairs consumed as they lie, ``act_into`` on the action
 rows, a callable -- is decided in one place, ``seat_actions``, for the partner's seat and the ego's.

@@ -330,7 +330,7 @@ OC_API int oc_policy_ppo_train_step(const oc_ppo_cfg *cfg, const oc_ppo_train *t
  * env (trainer.py:92-112: RecurrentPPO('MultiInputPolicy', ...), for the partner inside OnPolicyAgent) --
  * one LSTM cell of 64 units shared by actor and critic, its state kept per env and put back to zero
  * where an episode starts.  OUT OF SCOPE: hidden sizes other than 64, a separate critic LSTM.  (The update,
- * backpropagation through time: the section after this one.)
+ * backpropagation through time: the section after the next.)
  *
  * The network (gym-comm_amd/partners.py: LSTMActorCritic), per env, H = 64, F observation rows x, gates
  * in torch.nn.LSTMCell's order i, f, g, o:
@@ -413,13 +413,84 @@ OC_API int oc_policy_lstm_pack_head_bias(const float *b2, const float *bv, int32
 OC_API int oc_policy_lstm_ac(const oc_policy_lstm_player *pl, const double *timestep, int32_t F, int32_t C,
                              int32_t obs_type, int64_t n, void *stream);
 
+/* ---- windows of a rollout: states recorded mid-rollout, and minibatches of windows -----------------------
+ *
+ * What it stands in for: the way the reference's RecurrentPPO (sb3_contrib, seated by trainer.py:92-112 with
+ * n_steps = 5000 and batch_size = 1000) trains on stretches SHORTER than the rollout: its buffer keeps the LSTM
+ * state along the rollout, and a minibatch is a set of short stretches of the envs' sequences, each unrolled from
+ * the state recorded where it begins.  Here a rollout of T steps is cut into T / W windows of W steps, the seat's
+ * state is recorded where each window begins (oc_policy_window_snapshot, one launch per step in front of the
+ * cell's), and a minibatch of windows is PACKED into a "window batch" -- tensors laid out as a sink of W slots and
+ * E envs with a start state of their own (oc_policy_window_gather, one launch) -- which the update of the
+ * sections below unrolls exactly as it unrolls a whole sink.  Those sections' kernels are unchanged: to them a
+ * window batch IS a full sink with T = W and n = E, and envs = 0 .. E - 1.
+ *
+ * What windows mean for the gradient: a window's start state (h0, c0 of the batch) is a CONSTANT, as the
+ * rollout's start state is in the sections below; nothing flows across a window's first step, so a weight's
+ * gradient sees at most W steps of history (truncated backpropagation through time), while the forward's values
+ * are those of the whole sequence -- the recorded state is the one the rollout really had there.  An episode
+ * start inside a window cuts state and gradient as it does anywhere.
+ *
+ * OUT OF SCOPE: windows that do not divide the rollout (T % W != 0 is refused, not padded: a shorter last window
+ * would need per-sample masks, which the update does not have); a state recorded at every step; sb3_contrib's
+ * exact minibatches (contiguous chunks of the env-major flattened buffer, padded to the longest stretch).
+ *
+ * Sequence ids.  With n envs and T / W windows, sequence s = k n + env, 0 <= s < n T / W, is window k (slots
+ * k W .. k W + W - 1) of env `env`.  32 neighbouring envs of one window are 32 neighbouring ids: a shuffle in
+ * granules that divide n keeps a wave's reads of a row contiguous.
+ *
+ *   states   float [T / W][2][64][n]: states[k][0] = h and states[k][1] = c BEFORE the step recorded in slot k W
+ *            (so states[0] is the rollout's start state) */
+typedef struct {
+  const void *obs;            /* the sink's tensors (an oc_rollout_buf's): obs [T][F][n] of `obs_type` */
+  const double *timestep;     /* double [T][n] */
+  const int32_t *actions;     /* int32 [T][2][n] */
+  const float *log_probs, *advantages, *returns, *episode_starts, *values;   /* float [T][n] each */
+  const float *states;        /* float [T / W][2][64][n] (above) */
+  int64_t n;
+  int32_t T, W, F, obs_type;  /* obs_type: 0 int32, 1 int8, 2 float32 */
+} oc_window_src;
+
+typedef struct {              /* the same tensors laid out as a sink of W slots and E envs */
+  void *obs;                  /* [W][F][E] of the source's element type */
+  double *timestep;           /* double [W][E] */
+  int32_t *actions;           /* int32 [W][2][E] */
+  float *log_probs, *advantages, *returns, *episode_starts, *values;         /* float [W][E] each */
+  float *h0, *c0;             /* float [64][E]: the start state of each sequence */
+} oc_window_batch;
+
+/* One launch, capturable, never allocates or synchronises.  Every workgroup reads the sink's position word
+ * *pos (the slot the NEXT oc_rollout_add writes; a value outside 0 .. T - 1 is taken modulo T, as oc_rollout_add
+ * takes it) and, if slot % W == 0, the launch copies h and c, float [64][n] each, into states[slot / W], bit for
+ * bit; otherwise it writes nothing and costs an empty launch (a few workgroups per CU at most are started).  16-byte
+ * accesses where h, c and states are 16-byte aligned, scalar ones otherwise.  Launched in front of the cell's launch
+ * on the same stream it records the state before the step.  Checked before any device work: non-NULL pointers,
+ * W >= 1, T % W == 0, n >= 1, 64 n < 2^31. */
+OC_API int oc_policy_window_snapshot(const int64_t *pos, int32_t T, int32_t W, const float *h, const float *c,
+                                     float *states, int64_t n, void *stream);
+
+/* One launch, capturable, never allocates or synchronises.  seqs, int32 [E]: sequence ids (above), any order,
+ * repeats allowed; an id outside 0 .. n T / W - 1 is a caller error and is NOT checked on the device.  For
+ * sequence e = (k, env) of seqs and t = 0 .. W - 1, element (t, ., e) of every tensor of dst is element
+ * (k W + t, ., env) of the same tensor of src, copied bit for bit; h0[u][e] = states[k][0][u][env] and c0[u][e] =
+ * states[k][1][u][env].  e is the fastest-varying index on both sides.  No tensor of dst may overlap one of src.
+ * Checked before any device work: non-NULL pointers (all of both structs), W >= 1, T % W == 0, E >= 1, n >= 1,
+ * F >= 1, F + 2 <= 64, obs_type, T n < 2^31, 64 n < 2^31, W F E < 2^31.
+ *
+ * In a train sequence (the header's last section) the gather runs in front of every minibatch's step and is NOT
+ * held back when the sequence is halted: it writes only the window batch, the learner's own staging, and
+ * nothing the learner's state is made of -- no parameter, Adam word, image, statistic or sum. */
+OC_API int oc_policy_window_gather(const oc_window_src *src, const oc_window_batch *dst, const int32_t *seqs,
+                                   int32_t E, void *stream);
+
 /* ---- the recurrent seat's PPO update: forward over whole sequences, BPTT, clip, Adam, repack ----------
  *
  * What it restates: one minibatch of train() of the reference's RecurrentPPO (trainer.py:92-112 seats it) for
  * the network of the section above: advantage normalisation, the forward over whole recorded sequences, the
  * clipped loss, the gradient through time, the norm clip, Adam, and the repack of the seat's three images in
  * place.  OUT OF SCOPE:
- *   - truncated windows shorter than the rollout, and states recorded mid-rollout
+ *   - truncated windows inside the update: it unrolls the tensors it is given, whole (windows shorter than the
+ *     rollout reach it packed as a sink of their own: the section above)
  *   - the marginal-regularisation term
  *   - hidden sizes other than 64
  *   - a separate critic LSTM
@@ -544,7 +615,8 @@ OC_API int oc_policy_rppo_grad(const oc_rppo_cfg *cfg, const int32_t *envs, int3
  * mean(old_lp - lp); where it exceeds 1.5 target_kl no further epoch runs.  It is NOT sb3_contrib RecurrentPPO's
  * rule, which breaks in mid-epoch, before the minibatch that crosses the line is applied, on the estimator
  * mean((rho - 1) - log rho) (ppo_recurrent.py:407-412).  OUT OF SCOPE: sb3_contrib's mid-epoch break and its
- * estimator; truncated windows shorter than the rollout; the marginal-regularisation term.
+ * estimator; truncated windows inside the step (a minibatch of windows reaches it packed, by
+ * oc_policy_window_gather in front of it); the marginal-regularisation term.
  *
  * Value clipping, where c = hyper_ext[0] = clip_range_vf > 0: with old_v = values[t * n + env] the recorded value
  * of sample (t, env), in float32,
