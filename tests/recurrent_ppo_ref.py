@@ -8,6 +8,7 @@ header's equations, never from the packed images.
     clip / adam / adam_bound / HP              ppo_ref's
     make_case(T, n, envs, F, C, odt, seed...)  the inputs the CPU and the GPU tests share
     MUTANTS                                    bugs ``mutate`` plants
+    gpu_cases() / edge_cases()                 the cases a-c / d-g of the GPU tests
 
 ``emulate=True`` runs ``recurrent_ref.step(emulate=True)`` step by step -- each step from the previous one's
 state, stored as float32 -- and takes the derivatives where the header says the kernel does: at the network
@@ -18,7 +19,9 @@ products), sigma' = r (1 - r) and tanh' = 4 r (1 - r) from the unrounded r, the 
 Tolerances.  A derived bound through T steps of backpropagation is out of reach here; TOL_G and TOL_S are
 4 x the largest |kernel - loss_and_grad(emulate=True)| MEASURED on an MI355X over the cases a-c of
 tests/test_recurrent_ppo_gpu.py (figures below; measured, not a bound), and are kept honest by
-TOL_G <= MUT_MIN / 20: every planted bug moves some tensor at least twenty times further.
+TOL_G <= MUT_MIN / 20: every planted bug moves some tensor at least twenty times further.  ``edge_cases`` adds
+the shapes a full-size minibatch reaches; its 52-step case d has tolerances of its own, TOL_G_LONG / TOL_S_LONG,
+made the same way from d's own figures (``tolerances(name)`` picks the pair).
 """
 import numpy as np
 
@@ -46,6 +49,22 @@ TOL_S = 2.2e-6        # 4 x 5.36e-07, rounded up
 # the smallest relative move of any tensor's gradient under any mutant, over the cases in which the mutant
 # applies (tests/test_recurrent_ppo_cpu.py recomputes it and prints it)
 MUT_MIN = 0.0399
+
+# ---- measured on an MI355X, 2026-10-21, the cases of ``edge_cases`` (tests/test_recurrent_ppo_gpu.py) ----
+# the same two figures.  e, e48, f, g are short cases with a-c's arithmetic and keep TOL_G / TOL_S; their figures
+# are recorded only (each the larger of max_groups 0 and 1).  d runs 52 steps: d_0, d_1, d_7 are max_groups 0 (256
+# workgroups, 2 rounds), 1 (260 rounds) and 7 (38 rounds).
+MEASURED_EDGE = dict(grad=dict(d_0=1.796e-05, d_1=1.784e-05, d_7=1.792e-05, e=5.38e-06, e48=1.32e-06, f=2.16e-06,
+                               g=2.47e-06),
+                     stats=dict(d_0=6.45e-08, d_1=7.20e-08, d_7=6.45e-08, e=5.57e-07, e48=2.01e-07, f=5.82e-08,
+                                g=1.38e-06))
+MEASURED["grad"].update(MEASURED_EDGE["grad"])
+MEASURED["stats"].update(MEASURED_EDGE["stats"])
+# the long case's tolerances: 4 x the largest figure of d, rounded up -- the margin TOL_G has, for the same reason
+# (which fp16 neighbour an h rounds to differs between the kernel's float32 and the reference's float64) -- and
+# kept honest by TOL_G_LONG <= (the smallest mutant move of d) / 20 = 0.0515 / 20 (tests/test_recurrent_ppo_cpu.py)
+TOL_G_LONG = 7.2e-5   # 4 x 1.796e-05, rounded up
+TOL_S_LONG = 2.9e-7   # 4 x 7.20e-08, rounded up
 
 
 def test_hp(max_grad_norm=1e9):
@@ -103,16 +122,18 @@ def forward(case, emulate=True):
     return steps
 
 
-def loss_and_grad(case, hp, emulate=True, mutate=None):
+def loss_and_grad(case, hp, emulate=True, mutate=None, steps=None):
     """The header's loss over the B = E T samples of ``case`` and its gradient through time, in float64.
-    Returns (grads {name: array shaped as the module's parameter}, stats {name: value}, intermediates)."""
+    Returns (grads {name: array shaped as the module's parameter}, stats {name: value}, intermediates).
+    ``steps``: ``forward(case, emulate)`` made earlier (the intermediates' "steps"; it is only read): no mutant
+    touches the forward, and at T = 52 the forward is nearly all of the time."""
     if mutate is not None and mutate not in MUTANTS:
         raise ValueError("unknown mutant %r" % (mutate,))
     envs = np.asarray(case["envs"], np.int64)
     T, F, n = case["obs"].shape
     E = envs.shape[0]
     B = E * T
-    steps = forward(case, emulate)
+    steps = forward(case, emulate) if steps is None else steps
     gather = lambda a: np.asarray(a, np.float64)[:, envs].reshape(-1)  # noqa: E731  (sample i = t E + e)
     adv, ret, old = gather(case["adv"]), gather(case["ret"]), gather(case["old_lp"])
     logits = np.concatenate([s["logits"] for s in steps], axis=1)           # [4 + C][B]
@@ -193,8 +214,9 @@ def stats_diff(got, ref, names=STATS):
 
 def mutant_moves(case, hp):
     """{mutant: the largest relative move (``rel_diff``) it causes in any tensor of the emulated gradient}."""
-    ref = loss_and_grad(case, hp, emulate=True)[0]
-    return {m: max(rel_diff(loss_and_grad(case, hp, emulate=True, mutate=m)[0], ref).values()) for m in MUTANTS}
+    ref, _, inter = loss_and_grad(case, hp, emulate=True)
+    return {m: max(rel_diff(loss_and_grad(case, hp, emulate=True, mutate=m, steps=inter["steps"])[0], ref).values())
+            for m in MUTANTS}
 
 
 # ---- the shared inputs ---------------------------------------------------------------------------------------------
@@ -242,3 +264,34 @@ def gpu_cases():
     return [("a", make_case(1, 32, [5, 5], 14, 1, "int8", 11)),
             ("b", make_case(2, 40, eb, 29, 5, "int32", 12)),
             ("c", make_case(7, 100, ec, 62, 16, "float32", 13, scale=2, starts=(0, 3, 6)))]
+
+
+def edge_cases():
+    """The cases d, e, e48, f, g: the paths a full-size minibatch takes that a-c do not reach: (name, case).
+
+        d    T = 52, n = 136, 128 envs permuted + one repeat (E = 129, 5 tiles), F 30, C 3, int8, starts at t = 0, 1, 2,
+             17, 51: 260 (t, tile) items -- the default plan is 256 workgroups of 2 rounds, the second with 4 live
+             items; int8 rows beyond t = 0; F + 2 = 32, one full x tile; BPTT through 52 steps
+        e    T = 3, n = 40, 33 envs, F 31, C 2, int32, start at t = 1: F + 2 = 33, a second x tile with one live column
+        e48  e with F = 46: F + 2 = 48, three full x k-steps
+        f    T = 3, n = 40, 32 envs, F 15, C 1, int8, start at t = 2: F + 2 = 17; no idle lane; int8 rows at t = 1, 2
+        g    T = 6, n = 36, envs [7], F 47, C 7, float32, start at t = 2: F + 2 = 49; E = 1, 31 clamped lanes
+    """
+    rng = np.random.default_rng(77)
+    ed = rng.permutation(136)[:128]
+    ed = np.concatenate([ed, ed[:1]])                                        # one repeat
+    ee = rng.permutation(40)[:33]
+    ef = rng.permutation(40)[:32]
+    return [("d", make_case(52, 136, ed, 30, 3, "int8", 14, starts=(0, 1, 2, 17, 51))),
+            ("e", make_case(3, 40, ee, 31, 2, "int32", 15, starts=(1,))),
+            ("e48", make_case(3, 40, ee, 46, 2, "int32", 18, starts=(1,))),
+            ("f", make_case(3, 40, ef, 15, 1, "int8", 16, starts=(2,))),
+            ("g", make_case(6, 36, [7], 47, 7, "float32", 17, starts=(2,)))]
+
+
+LONG = ("d",)                            # the cases TOL_G_LONG / TOL_S_LONG are for
+
+
+def tolerances(name):
+    """(gradient, statistics) tolerance of the case ``name``."""
+    return (TOL_G_LONG, TOL_S_LONG) if name in LONG else (TOL_G, TOL_S)

@@ -108,6 +108,69 @@ def test_every_mutant_moves_the_emulated_gradient():
         rp.loss_and_grad(case, hp, mutate="nothing")
 
 
+_EDGE = {}
+
+
+def _edge(name):
+    """tests/recurrent_ppo_ref.py's edge cases, built once and never changed."""
+    if not _EDGE:
+        _EDGE.update(rp.edge_cases())
+    return _EDGE[name]
+
+
+def test_the_edge_cases_are_what_they_are_for():
+    d, e, e48, f, g = (_edge(k) for k in ("d", "e", "e48", "f", "g"))
+    assert [(c["T"], c["n"], len(c["envs"]), c["F"], c["C"], c["odt"]) for c in (d, e, e48, f, g)] == [
+        (52, 136, 129, 30, 3, "int8"), (3, 40, 33, 31, 2, "int32"), (3, 40, 33, 46, 2, "int32"), (3, 40, 32, 15, 1, "int8"),
+        (6, 36, 1, 47, 7, "float32")]
+    assert len(set(d["envs"].tolist())) == 128 and d["envs"][-1] == d["envs"][0] and list(d["envs"][:-1]) != sorted(d["envs"][:-1])
+    assert len(set(e["envs"].tolist())) == 33 and len(set(f["envs"].tolist())) == 32 and list(g["envs"]) == [7]
+    for c, starts in ((d, (0, 1, 2, 17, 51)), (e, (1,)), (e48, (1,)), (f, (2,)), (g, (2,))):
+        mine = c["es"][:, c["envs"]]
+        assert [t for t in range(c["T"]) if mine[t].any()] == list(starts)
+        assert all(0 < mine[t].sum() < len(c["envs"]) or len(c["envs"]) == 1 for t in starts)
+        assert c["obs"].dtype == np.dtype(c["odt"])
+    # some sequence of d starts at each of t = 0, 1, 2: three consecutive cuts of one carry
+    assert (d["es"][:3, d["envs"]].sum(axis=0) == 3).any()
+    # the int8 rows beyond t = 0 are not the rows of t = 0
+    assert not np.array_equal(d["obs"][1], d["obs"][0]) and not np.array_equal(f["obs"][2], f["obs"][0])
+
+
+def test_every_mutant_moves_the_edge_cases_twenty_tolerances():
+    """d, e, e48 and f: every mutant applies, and the smallest move is at least 20 x the tolerance of that case."""
+    hp = rp.test_hp()
+    for name in ("d", "e", "e48", "f"):
+        mv = rp.mutant_moves(_edge(name), hp)
+        tol_g = rp.tolerances(name)[0]
+        print(name, {m: "%.3g" % v for m, v in mv.items()}, "smallest %.4g" % min(mv.values()), "tolerance %.3g" % tol_g)
+        assert all(v > 0 for v in mv.values()), (name, mv)
+        assert min(mv.values()) >= 20 * tol_g, (name, min(mv.values()), tol_g)
+    assert rp.tolerances("d") == (rp.TOL_G_LONG, rp.TOL_S_LONG) and rp.tolerances("g") == (rp.TOL_G, rp.TOL_S)
+    # the long case's tolerances are 4 x its own measured figures, rounded up, and the short cases' figures lie
+    # within TOL_G / TOL_S
+    m = rp.MEASURED
+    for kind, tol in (("grad", rp.TOL_G_LONG), ("stats", rp.TOL_S_LONG)):
+        largest = max(m[kind][k] for k in ("d_0", "d_1", "d_7"))
+        assert 4 * largest <= tol <= 1.01 * 4 * largest, (kind, largest, tol)
+    assert all(m["grad"][k] <= rp.TOL_G and m["stats"][k] <= rp.TOL_S for k in ("e", "e48", "f", "g"))
+
+
+def test_reference_equals_torch_autograd_of_the_module_through_52_steps():
+    """emulate=False of case d against float64 autograd: the reference itself at T = 52, E = 129, five starts."""
+    case = _edge("d")
+    hp = rp.test_hp()
+    want, loss = _torch_grads(case, hp)
+    got, stats, _ = rp.loss_and_grad(case, hp, emulate=False)
+    print("loss", stats["loss"], loss)
+    assert abs(stats["loss"] - loss) <= 1e-12 * max(1.0, abs(loss))
+    for k in rp.NAMES:
+        assert got[k].shape == want[k].shape, k
+        scale = np.abs(want[k]).max()
+        err = np.abs(got[k] - want[k]).max() / scale
+        print(k, "%.3g" % err)
+        assert scale > 0 and err <= 1e-12, (k, err)
+
+
 def test_exports_struct_and_prototypes_match_the_header():
     from gym_comm_amd import _lib, learner, vec_env
     L = _policy_lib()
@@ -199,6 +262,27 @@ def test_plan_by_hand():
     assert L.oc_policy_rppo_plan(29, 2, 128, 65536, 0, plan) == 0
     assert list(plan) == [2048, 256, 1024, P, 2 * 97 + 416 * 128 * 65536 + 256 * P + 8 * 2048, 97, 6, 416]
     assert plan[4] > 2 ** 31
+
+
+def test_plan_by_hand_of_the_ragged_rounds():
+    """The plans tests/test_recurrent_ppo_gpu.py's ragged runs assert: Gw does not divide T tiles, so the last round
+    of the weight-gradient kernel has idle workgroups."""
+    L = _policy_lib()
+    plan = (ctypes.c_int64 * 8)()
+    d = _edge("d")
+    T, E, F, C = d["T"], len(d["envs"]), d["F"], d["C"]
+    assert (T, E, F, C) == (52, 129, 30, 3)
+    P = 256 * 32 + 16384 + 65 * 7 + 65                                       # F = 30, C = 3: 25096
+    assert L.oc_policy_rppo_plan(F, C, T, E, 0, plan) == 0                   # 260 items over the default cap
+    print("d, max_groups 0:", list(plan))
+    assert list(plan) == [5, 256, 2, P, 2 * 99 + 416 * 52 * 129 + 256 * P + 40, 99, 6, 416] and P == 25096
+    assert 256 * 2 - 52 * 5 == 252                                           # the second round: 4 live items of 256
+    assert L.oc_policy_rppo_plan(F, C, T, E, 7, plan) == 0
+    print("d, max_groups 7:", list(plan))
+    assert list(plan)[:3] == [5, 7, 38] and 7 * 38 == 266 and 52 * 5 == 260
+    assert L.oc_policy_rppo_plan(62, 16, 7, 96, 4, plan) == 0                # case c
+    print("c, max_groups 4:", list(plan))
+    assert list(plan)[:3] == [3, 4, 6] and 4 * 6 == 24 and 7 * 3 == 21
 
 
 @pytest.mark.parametrize("C", [1, 5, 16])

@@ -7,6 +7,9 @@ which each mechanism can fail:
     b   T = 2, n = 40, 33 envs, permuted    F 29, C 5, int32     one carry; a full tile + 1 lane; two x k-steps
     c   T = 7, n = 100, 96 envs, permuted,  F 62, C 16, float32  three tiles; four x k-steps; starts at t = 0, 3, 6;
         one repeat                                               weights x 2
+
+and on tests/recurrent_ppo_ref.py's ``edge_cases`` d, e, e48, f, g: the paths a full-size minibatch takes -- a ragged
+last round of the weight-gradient kernel, int8 rows beyond t = 0, F + 2 = 17, 32, 33, 48, 49, 52 steps, E = 1 and 32.
 """
 import copy
 import os
@@ -25,13 +28,14 @@ import recurrent_ppo_ref as rp  # noqa: E402
 pytestmark = pytest.mark.gpu
 DT = {"int32": torch.int32, "int8": torch.int8, "float32": torch.float32}
 _CASES = {}
+ALL = ["a", "b", "c", "d", "e", "e48", "f", "g"]
 
 
 def _case(name):
-    """The shared cases and their references, built once and never changed."""
-    if not _CASES:
+    """The shared cases and their references, built once (a family at its first use) and never changed."""
+    if name not in _CASES:
         hp = rp.test_hp()
-        for k, c in rp.gpu_cases():
+        for k, c in (rp.gpu_cases() if name in "abc" else rp.edge_cases()):
             _CASES[k] = (c, rp.loss_and_grad(c, hp, emulate=True))
     return _CASES[name]
 
@@ -68,7 +72,7 @@ def _bits(t):
     return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16) if t.dtype == torch.float16 else t
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c"])
+@pytest.mark.parametrize("name", ALL)
 def test_the_forward_is_T_chained_scoring_launches_bit_for_bit(name):
     case, _ = _case(name)
     e = _setup(case)
@@ -88,22 +92,29 @@ def test_the_forward_is_T_chained_scoring_launches_bit_for_bit(name):
     assert torch.isfinite(lp_out).all()
 
 
-@pytest.mark.parametrize("name", ["a", "b", "c"])
+@pytest.mark.parametrize("name", ALL)
 def test_the_gradient_and_the_statistics_against_the_reference_and_every_mutant_is_rejected(name):
-    case, (ref, stats, _) = _case(name)
+    case, (ref, stats, inter) = _case(name)
+    tol_g, tol_s = rp.tolerances(name)
     e = _setup(case)
     got, gstats = _grads(e)
     d = rp.rel_diff(got, ref)
     sd = rp.stats_diff(gstats, stats)
-    print("case", name, "grad", {k: "%.3g" % v for k, v in d.items()})
-    print("case", name, "stats", {k: "%.3g" % v for k, v in sd.items()})
-    assert max(d.values()) <= rp.TOL_G, d
-    assert max(sd.values()) <= rp.TOL_S, sd
+    print("case", name, "grad", {k: "%.3g" % v for k, v in d.items()}, "largest %.3g" % max(d.values()))
+    print("case", name, "stats", {k: "%.3g" % v for k, v in sd.items()}, "largest %.3g" % max(sd.values()))
+    assert max(d.values()) <= tol_g, d
+    assert max(sd.values()) <= tol_s, sd
+    if name == "g":
+        # one sequence does not separate every planted bug by twenty tolerances: the tolerance alone, and no
+        # tensor's gradient may be missing
+        assert all(np.abs(got[k]).max() > 0 for k in rp.NAMES), {k: np.abs(got[k]).max() for k in rp.NAMES}
+        return
     for m in rp.MUTANTS:
-        mref = rp.loss_and_grad(case, e.hp, emulate=True, mutate=m)[0]
+        mref = rp.loss_and_grad(case, e.hp, emulate=True, mutate=m, steps=inter["steps"])[0]
         if max(rp.rel_diff(mref, ref).values()) == 0:
+            assert name in "abc", (name, m)              # every mutant applies to d, e, e48 and f
             continue                                     # the mutant does not apply to this case (tests/test_recurrent_ppo_cpu.py)
-        assert max(rp.rel_diff(got, mref).values()) > rp.TOL_G, m
+        assert max(rp.rel_diff(got, mref).values()) > tol_g, m
 
 
 def test_a_starting_envs_old_state_reaches_nothing():
@@ -156,19 +167,64 @@ def test_the_same_call_gives_the_same_bits_and_one_workgroup_agrees():
     assert max(rp.rel_diff(g3, g1).values()) <= rp.TOL_G
 
 
+_ONE_GROUP = {}
+
+
+@pytest.mark.parametrize("name,max_groups,groups,per", [("c", 4, 4, 6), ("d", 0, 256, 2), ("d", 7, 7, 38)])
+def test_a_ragged_last_round_of_the_weight_gradient(name, max_groups, groups, per):
+    """Gw does not divide the T ceil(E / 32) items: in the last round the workgroups past the end skip the item, and
+    both of its barriers.  c, 4: 21 items in 24 slots; d, default cap: 260 in 512, the second round 4 live of 256;
+    d, 7: 260 in 266."""
+    case, (ref, stats, _) = _case(name)
+    tol_g, tol_s = rp.tolerances(name)
+    e = _setup(case, max_groups=max_groups)
+    tiles, Gw, rounds = e.learner.plan(e.E, e.T)[:3]
+    assert (Gw, rounds) == (groups, per) and Gw * rounds > tiles * e.T > Gw * (rounds - 1)
+    g1, s1 = _grads(e)
+    g2, s2 = _grads(e)
+    assert all(np.array_equal(g1[k], g2[k]) for k in g1) and s1 == s2
+    d, sd = rp.rel_diff(g1, ref), rp.stats_diff(s1, stats)
+    print("case", name, "max_groups", max_groups, "(Gw, per)", (Gw, rounds), "grad", {k: "%.3g" % v for k, v in d.items()},
+          "largest %.3g" % max(d.values()), "stats largest %.3g" % max(sd.values()))
+    assert max(d.values()) <= tol_g, d
+    assert max(sd.values()) <= tol_s, sd
+    if name not in _ONE_GROUP:
+        one = _setup(case, max_groups=1)
+        assert one.learner.plan(one.E, one.T)[1:3] == (1, tiles * e.T)
+        _ONE_GROUP[name] = _grads(one)[0]
+        d1 = rp.rel_diff(_ONE_GROUP[name], ref)
+        print("case", name, "max_groups 1: grad", {k: "%.3g" % v for k, v in d1.items()}, "largest %.3g" % max(d1.values()))
+        assert max(d1.values()) <= tol_g, d1
+    dd = rp.rel_diff(g1, _ONE_GROUP[name])
+    print("against max_groups 1:", {k: "%.3g" % v for k, v in dd.items()})
+    assert max(dd.values()) <= tol_g, dd
+
+
 def _images(e):
     return [t.clone() for t in e.seat._w] + [e.learner._bwd.clone()]
 
 
 def test_three_updates_are_adam_on_the_kernels_own_gradient_and_repack_the_images():
+    _updates_are_adam_and_repack("c", 3)
+
+
+@pytest.mark.parametrize("name", ["d", "e"])
+def test_an_update_of_an_edge_case_is_adam_and_repacks_the_images(name):
+    """d: the clip, Adam and the repack behind 52 steps' gradient, int8 rows and the default (ragged) plan; F + 2 = 32,
+    the timestep and the bias column are the last two of the second x k-step and the repack's ``k >= F + 2`` arm is
+    never taken.  e: F + 2 = 33, the third k-step holds the bias column and fifteen columns of that arm's zeros."""
+    _updates_are_adam_and_repack(name, 1)
+
+
+def _updates_are_adam_and_repack(name, updates):
     from gym_comm_amd.partners import pack_lstm, pack_lstm_bwd
-    case, _ = _case("c")
+    case, _ = _case(name)
     hp = rp.test_hp(max_grad_norm=0.05)                  # an active clip
     e = _setup(case, hp=hp)
     L = e.learner
     f64 = lambda t: t.detach().cpu().numpy().astype(np.float64).reshape(-1)  # noqa: E731
     flat = lambda: np.concatenate([f64(getattr(e.pol, k)) for k in rp.NAMES])  # noqa: E731
-    for step in (1, 2, 3):
+    for step in range(1, updates + 1):
         w, m, v = flat(), f64(L.m), f64(L.v)
         L.update(e.sink, e.envs)
         torch.cuda.synchronize()

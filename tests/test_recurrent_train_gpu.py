@@ -94,6 +94,32 @@ def test_device_train_and_its_graph_are_the_existing_update_bit_for_bit(granule)
         assert st["updates"] == 8 and st["epochs"] == 2 and not st["stopped"]
 
 
+def test_the_train_variant_of_the_long_case_is_the_existing_update_bit_for_bit():
+    """Case d of tests/recurrent_ppo_ref.py (T = 52, E = 129, int8 rows, F + 2 = 32) once through
+    oc_policy_recurrent_train_step -- the TRAIN = true instantiations, a unit of their own -- with value clipping
+    off and the default plan (256 workgroups, 2 rounds, the second with 4 live items), against update() on a twin."""
+    from gym_comm_amd import _lib
+    d = up._case("d")[0]
+    a, twin = up._setup(d), up._setup(d)
+    assert a.learner.plan(a.E, a.T)[:3] == (5, 256, 2) and a.sink.obs.dtype == torch.int8
+    ln = a.learner
+    assert float(ln.hyper_ext[0].item()) == 0.0               # clip_range_vf off
+    before = _state(a)
+    _lib.call(ln._L, "oc_policy_recurrent_train_step", ln._dev, ctypes.byref(ln._cfg(a.sink, a.E)),
+              ctypes.byref(ln._train_state(a.sink)), a.envs.data_ptr(), a.E)
+    twin.learner.update(twin.sink, twin.envs)
+    torch.cuda.synchronize()
+    names = ["param %d" % i for i in range(len(ln._params))] + ["m", "v", "step", "grad_flat", "stats"] \
+        + ["image %d" % i for i in range(len(a.seat._w))] + ["bwd"]
+    got, want = _state(a), _state(twin)
+    assert len(names) == len(got) == len(want)
+    for nm, x, y in zip(names, got, want):
+        assert torch.equal(_bits(x), _bits(y)), nm
+    assert int(ln.step.item()) == 1 and not _same(got, before)
+    assert torch.isfinite(ln.stats_t).all() and ln.stats()["bad"] == 0.0 and ln.grad_flat.abs().max() > 0
+    assert ln.ctl.cpu().tolist()[_lib.PPO_CTL["updates"]] == 1
+
+
 # ---- value clipping --------------------------------------------------------------------------------------------------
 def _vclip():
     """The value-clipping tests' inputs and reference, built once: every env of case c in one minibatch, in the

@@ -126,11 +126,13 @@ def _subset(count, size, seed):
 
 # ---- 1. the snapshot ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("aligned", [True, False])
-@pytest.mark.parametrize("n", [80, 1, 4099])
+@pytest.mark.parametrize("n", [80, 1, 4099, 12289])
 def test_the_snapshot_copies_exactly_where_a_window_begins(n, aligned):
     """T = 6, W = 3: pos 0 and 6 (wraps) write states[0], pos 3 writes states[1], pos 1 and 5 write nothing.  n = 1 and
     4 099 are single and odd row lengths; ``aligned=False`` hands h over 4 bytes past a 16-byte boundary, which takes
-    the scalar path for everything."""
+    the scalar path for everything.  n = 12 289 is beyond the cap of 1 024 workgroups: the 64 n / 2 float4 pairs ask
+    for 1 537, so the strided loop's second pass is partly full (the scalar path asks for 3 073: three full passes and
+    64 elements of a fourth)."""
     from gym_comm_amd import _lib
     L = _lib.load(lib="policy")
     T, W = 6, 3
